@@ -11,7 +11,15 @@ and weight-layout refresh, in bf16 compute with fp32 master weights.
 
 Launch: `python bench.py --gpus 1 --steps K --warmup W`, or for N>1
 `python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N`.
-Rank 0 prints ONE JSON line.
+Rank 0 prints ONE JSON line; `ms_per_step` in it is the wall time of one timed step.
+
+A plain run does only what the headline figure needs: set-up (kernel choices come from the shipped
+selection database, the step mode from a short trial of the applicable modes), `--warmup` steps,
+`--steps` timed steps, the result line. `--dump-outputs DIR` then runs the timed path once more
+from the initial state (outside the timed region) and writes what that step computed as
+`DIR/<name>.npy` (see dump_outputs and the comment at its call). `--full` is where secondary
+measurements (other precisions or sizes, baselines, per-kernel figures) go; the benchmark has none
+today, so the flag changes nothing yet.
 """
 from __future__ import annotations
 
@@ -35,6 +43,45 @@ BASELINE_IMG_S = {
 }
 
 
+# --dump-outputs: a buffer with more elements than this is written as a fixed, seeded sample of
+# that many (16 MB of float32 each; three arrays, so a dump stays under 64 MB)
+DUMP_SAMPLE = 4 << 20
+DUMP_SEED = 20240229
+
+
+def dump_outputs(ex, out_dir):
+    """Write what a caller of the training step gets back from it -- the per-example loss of its
+    forward pass and the state its update produced (fp32 master weights, BN moving statistics) --
+    as out_dir/<name>.npy in float32. main() calls this after one step of the timed path from the
+    seeded initial state on the seeded batch, so two builds run with the same arguments dump
+    comparable arrays. Comparable, not equal: the default step sums BN statistics and weight
+    gradients with float atomics, and a one-ulp difference early in the bf16 network reaches the
+    later layers as full bf16 rounding noise. Two runs of one build on an MI355X (ResNet-50,
+    batch 128) differed in relative L2 by 6e-6 (bn_moving), 2e-3 (loss) and 7e-3 (weights). The
+    logits (3.5e-2) and the momentum buffer, which after one step is the raw gradient (0.79),
+    are dominated by that noise and are not written."""
+    import numpy as np
+    import torch
+
+    torch.cuda.synchronize()
+    os.makedirs(out_dir, exist_ok=True)
+
+    def sample(t):
+        if t.numel() <= DUMP_SAMPLE:
+            return t
+        g = torch.Generator(device="cpu").manual_seed(DUMP_SEED)
+        idx = torch.randint(0, t.numel(), (DUMP_SAMPLE,), generator=g).sort().values
+        return t.reshape(-1)[idx.to(t.device)]
+
+    arrays = {"loss": ex.loss_vec, "weights": ex.P.master, "bn_moving": ex.P.bn_state}
+    total = 0
+    for name, t in arrays.items():
+        a = np.ascontiguousarray(sample(t.detach()).float().cpu().numpy())
+        total += a.nbytes
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    assert total <= 64 * 1000 * 1000, total
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -55,7 +102,17 @@ def main():
     ap.add_argument("--shard_optimizer", type=int, default=0, help="ZeRO-1 sharded optimizer (N > 1)")
     ap.add_argument("--allreduce_wire", default="fp32", choices=["fp32", "bf16"],
                     help="gradient dtype on the wire (bf16: half the all-reduce bytes)")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR",
+                    help="after the timed steps, run the timed path once more from the initial state and write what "
+                         "that step computed (per-example loss, updated weights, BN moving statistics) as "
+                         "DIR/<name>.npy (float32, rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the benchmark's secondary measurements (anything beyond the headline figure "
+                         "belongs behind this flag; a plain run only sets up, warms up, times --steps steps and "
+                         "prints the result line)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     # the result line is the ONLY thing on stdout: libraries that print banners there (RCCL's
     # version block at communicator init) are sent to stderr at the file-descriptor level
     sys.stdout.flush()
@@ -134,6 +191,8 @@ def main():
     g = torch.Generator(device="cpu").manual_seed(rank)
     ex.labels.copy_(torch.randint(0, spec.num_classes, (args.batch_size,), generator=g, dtype=torch.int32))
     ex.set_lr(0.1)
+    # --dump-outputs replays one step from this state after the timed steps (see below)
+    initial = [t.clone() for t in (ex.P.master, ex.P.momentum, ex.P.bn_state)] if args.dump_outputs else None
 
     def step():
         ex.forward(train=True)
@@ -316,6 +375,22 @@ def main():
         if plan is not None and mode.startswith("plan"):
             # native segments between the engine's Python-issued bucket collectives
             dp["plan_report_cuts"] = sum(1 for _, act in plan.cuts if isinstance(act, tuple))
+    if initial is not None:
+        # --dump-outputs: the state the timed steps end in is not reproducible (they train on, and
+        # the weight gradients are summed with float atomics, so rounding differences between two
+        # runs grow step by step: after ~150 steps two runs of ONE build differed by 13-32 % in
+        # relative L2). So the dumped step is the timed path run once more from the initial weights,
+        # momentum and BN statistics -- the same call the timed loop makes, on inputs that are the
+        # same in every run, outside the timed region.
+        torch.cuda.synchronize()
+        for buf, init in zip((ex.P.master, ex.P.momentum, ex.P.bn_state), initial):
+            buf.copy_(init)
+        ex.sync_weights()
+        torch.cuda.synchronize()
+        run()
+        torch.cuda.synchronize()
+        if rank == 0:
+            dump_outputs(ex, args.dump_outputs)
     if rank == 0:
         base = BASELINE_IMG_S.get(args.dataset, {}).get(world) \
             if (args.width == 1 and args.resnet_size == 50 and spec.image_size in (224, 32)) else None

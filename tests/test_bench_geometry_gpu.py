@@ -5,10 +5,15 @@ split-K / stream-K tiles, and weight-gradient launches with their split counts -
 compared with the fp32 reference of the same op (ops.backend.RefBackend on the GPU: test oracle
 only) on fresh bf16-rounded random operands.
 
-The launches are recorded from one real autotuned forward + backward of the executor at collection
-time (pytest_generate_tests: one test id per distinct launch, no unused parametrised slots), so the
-test covers exactly the (geometry, configuration) pairs bench.py times."""
+The launches are recorded from one real autotuned forward + backward of the executor: one test id
+per distinct launch, no unused parametrised slots, so the test covers exactly the (geometry,
+configuration) pairs bench.py times. The ids are listed in tests/golden/bench_geometry_launches.json,
+so the suite has the same test ids whether or not a GPU is visible when it is collected;
+test_bench_geometry_records_the_step fails when the recorded step and that list differ
+(`PYTHONPATH=. python tests/test_bench_geometry_gpu.py` on a GPU rewrites the list)."""
 import ctypes
+import json
+import os
 
 import pytest
 import torch
@@ -21,6 +26,7 @@ pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not torch.cuda.is_available(),
 
 BATCH = 128
 _REC = {}
+LAUNCHES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "bench_geometry_launches.json")
 
 
 def _rel(a, b):
@@ -72,22 +78,44 @@ def _wgrad_id(k) -> str:
     return f"{xs[1]}x{xs[2]}x{xs[3]}-{outs[0]}-{outs[1]}x{outs[2]}s{st}" + ("-p" if pro else "")
 
 
+# test function -> (recorded kind, name in the stored list, id function)
+_KINDS = {"test_bench_geometry_conv": ("fwd", "conv", _conv_id),
+          "test_bench_geometry_wgrad": ("wgrad", "wgrad", _wgrad_id)}
+
+
+def _recorded_ids(kind, idf) -> dict:
+    """{test id: launch key} of the recorded step, in the order of the ids' index prefix."""
+    keys = sorted(_record()[kind], key=str)
+    return {f"{i:02d}-{idf(k)}": k for i, k in enumerate(keys)}
+
+
+def _key_of(test, launch):
+    kind, _, idf = _KINDS[test]
+    ids = _recorded_ids(kind, idf)
+    assert launch in ids, f"{launch} is listed in {LAUNCHES} but the recorded step has no such launch"
+    return ids[launch]
+
+
 def pytest_generate_tests(metafunc):
     """One test per distinct launch of the recorded step (ids name the geometry)."""
-    kinds = {"test_bench_geometry_conv": ("fwd", _conv_id), "test_bench_geometry_wgrad": ("wgrad", _wgrad_id)}
-    if metafunc.function.__name__ not in kinds:
+    if metafunc.function.__name__ not in _KINDS:
         return
-    kind, idf = kinds[metafunc.function.__name__]
-    keys = sorted(_record()[kind], key=str) if torch.cuda.is_available() else []
-    metafunc.parametrize("key", keys, ids=[f"{i:02d}-{idf(k)}" for i, k in enumerate(keys)])
+    with open(LAUNCHES) as f:
+        listed = json.load(f)[_KINDS[metafunc.function.__name__][1]]
+    metafunc.parametrize("launch", listed, ids=listed)
 
 
 def test_bench_geometry_records_the_step():
     r = _record()
     assert len(r["fwd"]) > 0 and len(r["wgrad"]) > 0, (len(r["fwd"]), len(r["wgrad"]))
+    with open(LAUNCHES) as f:
+        listed = json.load(f)
+    for kind, name, idf in _KINDS.values():   # exactly the recorded launches: none missing, none unused
+        assert list(_recorded_ids(kind, idf)) == listed[name], name
 
 
-def test_bench_geometry_conv(key):
+def test_bench_geometry_conv(launch):
+    key = _key_of("test_bench_geometry_conv", launch)
     r = _record()
     be, keys = r["be"], sorted(r["fwd"], key=str)
     i = keys.index(key)
@@ -150,7 +178,8 @@ def test_bench_geometry_conv(key):
         assert _rel(s[:K], st_ref[:K]) < tol and _rel(s[K:], st_ref[K:]) < tol, (keys[i], cfg)
 
 
-def test_bench_geometry_wgrad(key):
+def test_bench_geometry_wgrad(launch):
+    key = _key_of("test_bench_geometry_wgrad", launch)
     r = _record()
     be, ex = r["be"], r["ex"]
     keys = sorted(r["wgrad"], key=str)
@@ -170,3 +199,9 @@ def test_bench_geometry_wgrad(key):
     out_ref = torch.zeros(*outs, device=dev)
     RefBackend(dev).conv_wgrad(x.float(), dy.float(), out_ref, g, in_bn=in_bn, relu_in=relu_in)
     assert _rel(out, out_ref) < 1e-2, (k, be.wgrad_ns.get(be.wgrad_key(be.wgrad_args(x, dy, out, g, in_bn))))
+
+
+if __name__ == "__main__":   # rewrite the list of launches from a step recorded on this GPU
+    with open(LAUNCHES, "w") as f:
+        json.dump({name: list(_recorded_ids(kind, idf)) for kind, name, idf in _KINDS.values()}, f, indent=1)
+        f.write("\n")
