@@ -1,7 +1,7 @@
 // drn_conv.h — argument blocks for the implicit-GEMM convolution kernels.
 //
 // These are plain-old-data structs so that the Python runtime can build them once per layer
-// at plan time (ctypes mirror in distributed_resnet_tensorflow_amd/ops/hip.py) and pass a
+// at plan time (ctypes mirror in distributed_resnet_tensorflow_amd/ops/_lib.py) and pass a
 // pointer per launch; the field order here and there must match exactly.
 #pragma once
 #include <stdint.h>
@@ -134,8 +134,9 @@ struct DrnConvFwdArgs {
   // of a y tensor of spatial size out_H x out_W (residual uses the same mapping).
   // out_stride == 0 means the identity mapping (y is [N][P][Q][K]).
   int32_t out_H, out_W, out_stride, out_oh, out_ow;
-  // Kernel configuration for drn_conv_fwd2: -1 automatic, 0..7 an LDS-DMA tile configuration
-  // (DRN_GLDS_CONFIGS), 100 the register-staged kernel.
+  // Kernel configuration for drn_conv_fwd2: -1 automatic, 0 .. drn_conv_glds_num_cfgs() - 1 an
+  // LDS-DMA tile configuration (kGldsCfg, conv_fwd.hip), 100 the register-staged kernel,
+  // drn_conv_nk_cfg0() + i a narrow-output (K = 16 / 32) one; drn_conv_cfg_info describes an id.
   int32_t cfg;
   // stats holds stats_rep replicas [rep][2][K]; block b adds into replica b % rep, so no
   // address collects more than blocks/rep atomics (same-address float atomics serialize).
@@ -187,6 +188,15 @@ struct DrnConvFwdArgs {
   unsigned* ks_tickets;
   int32_t ksplit;
   int32_t sk_blocks;
+};
+
+// What drn_conv_cfg_info reports about a configuration id (ctypes mirror in ops/_lib.py).
+struct DrnConvCfgInfo {
+  int32_t kind;            // 0: LDS-DMA tile configuration, 1: narrow-output (register-operand) one
+  int32_t bp, bc;          // block tile: output pixels x output channels
+  int32_t waves_p, ns, nw; // waves along the pixels, stage depth (LDS stages; 0: none), waves
+  int32_t bk, nh;          // k per stage, channel slices of the epilogue
+  int32_t il, ks;          // interleaved LDS-DMA issue; split-K / stream-K capable
 };
 
 // dW[K][R][S][C] (+)= sum_{n,p,q} dy[n,p,q,k] * x[n, p*st-pad+r, q*st-pad+s, c]

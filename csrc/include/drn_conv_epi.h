@@ -1,8 +1,8 @@
 // drn_conv_epi.h -- device helpers of the implicit-GEMM convolution kernels (conv_fwd.hip,
-// stem.hip): the fused
+// conv_wgrad.hip, stem.hip): the fused
 // epilogue (LDS-staged fp32 tile -> coalesced bf16 rows, residual add, strided output map,
-// next-BN statistics or fused BN-backward reduction), the LDS-DMA issue helpers and the
-// swizzle of the 128-byte LDS rows.
+// next-BN statistics or fused BN-backward reduction), the LDS-DMA issue helpers (glds16,
+// wait_vmcnt), the swizzle of the 128-byte LDS rows and the DRN_CONV_TRACE timeline record.
 #pragma once
 #include "drn_common.h"
 #include "drn_conv.h"
@@ -14,6 +14,27 @@ __device__ __forceinline__ unsigned long long drn_realtime() {
   asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t));
   return t;
 }
+
+#ifdef DRN_CONV_TRACE
+// Per-workgroup timeline record of the LDS-DMA kernels (a -DDRN_CONV_TRACE diagnostics build):
+// trace[4 * wg] = {start, main-loop end, end} in s_memrealtime ticks (100 MHz) + HW_ID / XCC_ID,
+// written once the workgroup's stores have retired.
+__device__ __forceinline__ void conv_trace_record(unsigned long long* trace, size_t wg, unsigned long long t_start,
+                                                  unsigned long long t_loop) {
+  if (trace == nullptr) return;
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const unsigned hw = __builtin_amdgcn_s_getreg((31 << 11) | 4);
+    const unsigned xcc = __builtin_amdgcn_s_getreg((15 << 11) | 20);
+    unsigned long long* r = trace + 4 * wg;
+    r[0] = t_start;
+    r[1] = t_loop;
+    r[2] = drn_realtime();
+    r[3] = ((unsigned long long)xcc << 32) | hw;
+  }
+}
+#endif
 
 // Sum of x over the lanes of a wave that are congruent mod CHR (CHR = 2..32, a power of two):
 // row rotations by CHR, 2*CHR .. 8 inside each 16-lane DPP row, then the cross-row partners via
@@ -345,7 +366,10 @@ typedef __attribute__((address_space(1))) const void drn_gbl_void;
 __device__ __forceinline__ void glds16(const void* src, char* lds_base) {
   __builtin_amdgcn_global_load_lds((drn_gbl_void*)src, (drn_lds_void*)lds_base, 16, 0, 0);
 }
-
+// glds16 expanded at the call site (conv_wgrad.hip: behind glds16's parameter its __restrict__
+// source pointers lose their no-alias scope, and hipcc schedules those main loops differently)
+#define DRN_GLDS16(src, lds) \
+  __builtin_amdgcn_global_load_lds((drn::drn_gbl_void*)(src), (drn::drn_lds_void*)(lds), 16, 0, 0)
 
 template <int N>
 __device__ __forceinline__ void wait_vmcnt() {

@@ -24,6 +24,13 @@
 #include "drn_conv.h"
 #include "drn_conv_epi.h"
 #include <stdlib.h>
+#include <array>
+
+#ifdef DRN_ISO_NOLOOP  // bound isolation (scripts/conv_bound_iso.py): prologue + epilogue only
+#define ISO_T(T) 0
+#else
+#define ISO_T(T) (T)
+#endif
 
 namespace drn {
 
@@ -296,12 +303,19 @@ __device__ __forceinline__ void kstep_next(int& r, int& s, int& ci, int R, int S
 // on another (no deadlock at any residency); the hand-off is the agent-scope release / acquire
 // pair of the CDNA4 guide (G16). For under-filled grids (e.g. 196 tiles of a 7x7-stage 3x3
 // conv on 256 CUs) it trades 64 KB of partial traffic per extra split for a full chip.
-template <int BP, int BC, int WAVES_P, int NS, int NW = 4, bool PF = true, int BK = 64, bool PRO = false,
-          bool SROW = false, int NH = 1, bool KS = false, bool IL = false>
+//
+// Variant flags of the LDS-DMA kernels (template parameter F): kPF = epilogue operands (residual /
+// BN-backward input) prefetched during the main loop, kPRO / kSROW / kKS as above, kIL = the next
+// stage's LDS-DMA pieces issued between the MFMAs (see the main loop).
+enum : unsigned { kPF = 1u, kPRO = 2u, kSROW = 4u, kKS = 8u, kIL = 16u };
+
+template <int BP, int BC, int WAVES_P, int NS, int NW, int BK, int NH, unsigned F>
 __device__ __forceinline__ void conv_fwd_glds_tile(const DrnConvFwdArgs& a, const void* __restrict__ zero, char* smem,
                                                    int bid, int ksn, int ksi, int ks_stride, int t_beg_in,
                                                    int t_cnt_in) {
+  constexpr bool PF = F & kPF, PRO = F & kPRO, SROW = F & kSROW, KS = F & kKS, IL = F & kIL;
   static_assert(BK == 64 || BK == 32, "k per stage");
+  static_assert(!SROW || !IL, "row-staged narrow convs: plain stage issue only");
   static_assert(!SROW || BK == 64, "row-staged narrow convs: 64-deep stages");
   constexpr int NT = NW * 64;
   constexpr int WAVES_C = NW / WAVES_P;
@@ -510,9 +524,11 @@ __device__ __forceinline__ void conv_fwd_glds_tile(const DrnConvFwdArgs& a, cons
   EpiPre<BP, BC / NH, NT, PF> epre;
   if constexpr (NH == 1)
     epi_prefetch<BP, BC, NT, PF>(a, m0, c0, M, epre);  // residual / BN inputs in flight during the main loop
+#ifndef DRN_ISO_NOLOAD
 #pragma unroll
   for (int s = 0; s < D; ++s)
     if (s < T) issue(s);
+#endif
   if constexpr (PRO) {
     if (a.in_fin.stats != nullptr) {
       // consumer-side BN finalize: scale/shift straight from the statistics replicas (the
@@ -527,7 +543,7 @@ __device__ __forceinline__ void conv_fwd_glds_tile(const DrnConvFwdArgs& a, cons
     }
     __syncthreads();
   }
-  for (int t = 0; t < T; ++t) {
+  for (int t = 0; t < ISO_T(T); ++t) {
     // retire stage t: the stages issued after it (up to D-1) may stay in flight
     if (t + D - 1 < T) wait_vmcnt<G * (D - 1)>();
     else wait_vmcnt<0>();
@@ -566,27 +582,47 @@ __device__ __forceinline__ void conv_fwd_glds_tile(const DrnConvFwdArgs& a, cons
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     const char* st = smem + (t % NS) * STAGE;
-    if constexpr (IL && !SROW) {
-      // the next stage's LDS-DMA pieces spread between this stage's MFMAs: the DMA issue cost
-      // (~0.1 us per piece per wave) hides under the matrix pipe instead of idling it after
-      // every barrier while all waves issue in lockstep
-      const bool more = t + D < T;
-      const int nslot = (t + D) % NS;
-      constexpr int Q = (BK / 32) * MI * MJ;
-      constexpr int STEP = Q / (G + 1) > 0 ? Q / (G + 1) : 1;
+    // plain: the next stage's LDS-DMA pieces all issued here, ahead of the MFMAs.
+    // IL: spread between this stage's MFMAs instead: the DMA issue cost (~0.1 us per piece per
+    // wave) hides under the matrix pipe instead of idling it after every barrier while all waves
+    // issue in lockstep
+#ifdef DRN_ISO_NOLOAD  // bound isolation: no LDS-DMA (stages keep whatever the LDS held)
+    const bool more = false;
+#else
+    const bool more = t + D < T;
+#endif
+    const int nslot = (t + D) % NS;
+    if constexpr (!IL)
+      if (more) issue(nslot);
+    constexpr int Q = (BK / 32) * MI * MJ;
+    constexpr int STEP = Q / (G + 1) > 0 ? Q / (G + 1) : 1;
+    constexpr bool PRIO = !IL && NW == 8;  // keeps the MFMA cluster together (guide T5)
 #pragma unroll
-      for (int kh = 0; kh < BK / 32; ++kh) {
-        const int slot = ((kh * 4 + fk) ^ swz) * 16;
-        bf16x8_t af[MI], bfr[MJ];
+    for (int kh = 0; kh < BK / 32; ++kh) {
+      const int slot = ((kh * 4 + fk) ^ swz) * 16;
+      bf16x8_t af[MI], bfr[MJ];
+#ifdef DRN_ISO_NOREAD  // bound isolation: operands without LDS reads
 #pragma unroll
-        for (int i = 0; i < MI; ++i) af[i] = *reinterpret_cast<const bf16x8_t*>(st + aoff[i] + slot);
+      for (int i = 0; i < MI; ++i) asm volatile("" : "=v"(af[i]));
 #pragma unroll
-        for (int j = 0; j < MJ; ++j) bfr[j] = *reinterpret_cast<const bf16x8_t*>(st + boffl[j] + slot);
+      for (int j = 0; j < MJ; ++j) asm volatile("" : "=v"(bfr[j]));
+#else
 #pragma unroll
-        for (int i = 0; i < MI; ++i)
+      for (int i = 0; i < MI; ++i) af[i] = *reinterpret_cast<const bf16x8_t*>(st + aoff[i] + slot);
 #pragma unroll
-          for (int j = 0; j < MJ; ++j) {
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
+      for (int j = 0; j < MJ; ++j) bfr[j] = *reinterpret_cast<const bf16x8_t*>(st + boffl[j] + slot);
+#endif
+      if constexpr (PRIO) __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+      for (int i = 0; i < MI; ++i)
+#pragma unroll
+        for (int j = 0; j < MJ; ++j) {
+#ifdef DRN_ISO_NOMFMA  // bound isolation: loads + fragment reads only
+          asm volatile("" ::"v"(af[i]), "v"(bfr[j]));
+#else
+          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
+#endif
+          if constexpr (IL) {
             const int q = (kh * MI + i) * MJ + j + 1;
             if (q % STEP == 0 && q / STEP <= G && more) {
               __builtin_amdgcn_sched_barrier(0);
@@ -594,31 +630,15 @@ __device__ __forceinline__ void conv_fwd_glds_tile(const DrnConvFwdArgs& a, cons
               __builtin_amdgcn_sched_barrier(0);
             }
           }
-      }
+        }
+      if constexpr (PRIO) __builtin_amdgcn_s_setprio(0);
+    }
+    if constexpr (IL) {
       if (Q / STEP < G && more) {  // (fewer MFMAs than pieces: the rest now)
 #pragma unroll
         for (int g = Q / STEP; g < G; ++g) issue_piece(nslot, g);
       }
       if (more) issue_advance();
-      asm volatile("" ::: "memory");
-      continue;
-    }
-    if (t + D < T) issue((t + D) % NS);
-#pragma unroll
-    for (int kh = 0; kh < BK / 32; ++kh) {
-      const int slot = ((kh * 4 + fk) ^ swz) * 16;
-      bf16x8_t af[MI], bfr[MJ];
-#pragma unroll
-      for (int i = 0; i < MI; ++i) af[i] = *reinterpret_cast<const bf16x8_t*>(st + aoff[i] + slot);
-#pragma unroll
-      for (int j = 0; j < MJ; ++j) bfr[j] = *reinterpret_cast<const bf16x8_t*>(st + boffl[j] + slot);
-      if constexpr (NW == 8) __builtin_amdgcn_s_setprio(1);  // keeps the MFMA cluster together (guide T5)
-#pragma unroll
-      for (int i = 0; i < MI; ++i)
-#pragma unroll
-        for (int j = 0; j < MJ; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
-      if constexpr (NW == 8) __builtin_amdgcn_s_setprio(0);
     }
     asm volatile("" ::: "memory");
   }
@@ -672,37 +692,23 @@ __device__ __forceinline__ void conv_fwd_glds_tile(const DrnConvFwdArgs& a, cons
   if constexpr (NH == 1) conv_epilogue<BP, BC, WP, WC, MI, MJ, NT, PF>(a, smem, acc, wp, wc, m0, c0, M, epre);
   else conv_epilogue_sliced<BP, BC, WP, WC, MI, MJ, NT, NH>(a, smem, acc, wp, wc, m0, c0, M);
 #ifdef DRN_CONV_TRACE
-  if (trace != nullptr) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) {
-      const unsigned hw = __builtin_amdgcn_s_getreg((31 << 11) | 4);
-      const unsigned xcc = __builtin_amdgcn_s_getreg((15 << 11) | 20);
-      unsigned long long* r = trace + 4 * (size_t)blockIdx.x;
-      r[0] = t_start;
-      r[1] = t_loop;
-      r[2] = drn_realtime();
-      r[3] = ((unsigned long long)xcc << 32) | hw;
-    }
-  }
+  conv_trace_record(trace, blockIdx.x, t_start, t_loop);
 #endif
 }
 
-template <int BP, int BC, int WAVES_P, int NS, int NW = 4, bool PF = true, int BK = 64, bool PRO = false,
-          bool SROW = false, int NH = 1, bool KS = false, bool IL = false>
+template <int BP, int BC, int WAVES_P, int NS, int NW, int BK, int NH, unsigned F>
 __global__ __launch_bounds__(NW * 64) void conv_fwd_glds_kernel(DrnConvFwdArgs a, const void* __restrict__ zero) {
   extern __shared__ __attribute__((aligned(1024))) char smem[];
   const int lin = xcd_remap(blockIdx.x, gridDim.x);  // (a tile's splits stay on one XCD)
-  if constexpr (KS) {
+  if constexpr (F & kKS) {
     const int ksn = a.ksplit;
     const int bid = lin / ksn, ksi = lin - bid * ksn;
     const int t_all = (a.R * a.S * a.C) / BK;
     const int t_beg = (int)((long)ksi * t_all / ksn);
     const int t_cnt = (int)((long)(ksi + 1) * t_all / ksn) - t_beg;
-    conv_fwd_glds_tile<BP, BC, WAVES_P, NS, NW, PF, BK, PRO, SROW, NH, KS, IL>(a, zero, smem, bid, ksn, ksi, ksn, t_beg,
-                                                                             t_cnt);
+    conv_fwd_glds_tile<BP, BC, WAVES_P, NS, NW, BK, NH, F>(a, zero, smem, bid, ksn, ksi, ksn, t_beg, t_cnt);
   } else {
-    conv_fwd_glds_tile<BP, BC, WAVES_P, NS, NW, PF, BK, PRO, SROW, NH, KS, IL>(a, zero, smem, lin, 1, 0, 1, 0, 0);
+    conv_fwd_glds_tile<BP, BC, WAVES_P, NS, NW, BK, NH, F>(a, zero, smem, lin, 1, 0, 1, 0, 0);
   }
 }
 
@@ -712,8 +718,10 @@ __global__ __launch_bounds__(NW * 64) void conv_fwd_glds_kernel(DrnConvFwdArgs a
 // arriving contributor (partials summed in contributor order: bitwise reproducible); nobody
 // waits. Every CU gets the same number of MFMA k-stages whatever the tile count (98 / 196 / 392
 // tiles of the ResNet-50 layers against 256 CUs).
-template <int BP, int BC, int WAVES_P, int NS, int NW = 4, int BK = 64, bool PRO = false, int NH = 1, bool IL = false>
+// (F: kKS | the launch's kPRO / kIL; never kPF, see below)
+template <int BP, int BC, int WAVES_P, int NS, int NW, int BK, int NH, unsigned F>
 __global__ __launch_bounds__(NW * 64) void conv_fwd_glds_sk_kernel(DrnConvFwdArgs a, const void* __restrict__ zero) {
+  static_assert((F & kKS) && !(F & (kPF | kSROW)), "stream-K: split-capable plain / PRO kernels");
   extern __shared__ __attribute__((aligned(1024))) char smem[];
   // (32-bit unit arithmetic: the launcher checks tiles x k-stages x grid < 2^31)
   const unsigned G = gridDim.x;
@@ -737,11 +745,11 @@ __global__ __launch_bounds__(NW * 64) void conv_fwd_glds_sk_kernel(DrnConvFwdArg
       __syncthreads();  // the previous segment's LDS use is over
       // a consumer-side BN finalize publishes (and moves the moving averages) once: in the
       // first segment of workgroup 0, not again if that workgroup's range spans several tiles
-      if constexpr (PRO) a.in_fin.publish = 0;
+      if constexpr (F & kPRO) a.in_fin.publish = 0;
     }
     // (no epilogue-operand prefetch: most segments end in a partial tile, not an epilogue)
-    conv_fwd_glds_tile<BP, BC, WAVES_P, NS, NW, false, BK, PRO, false, NH, true, IL>(
-        a, zero, smem, (int)tile, (int)(bl - bf + 1), (int)(b - bf), a.ksplit, (int)t0, (int)(t1 - t0));
+    conv_fwd_glds_tile<BP, BC, WAVES_P, NS, NW, BK, NH, F>(a, zero, smem, (int)tile, (int)(bl - bf + 1), (int)(b - bf),
+                                                           a.ksplit, (int)t0, (int)(t1 - t0));
     first = false;
     u = tend;
   }
@@ -890,9 +898,12 @@ __global__ __launch_bounds__(NW * 64) void conv_fwd_nk_kernel(DrnConvFwdArgs a) 
 static int cfin_max_blocks();
 
 // id -> (MI, MJ): 16-channel outputs with 32 / 64 pixels per wave, 32-channel with 16 / 32 / 64
-#define DRN_NK_CONFIGS(X) X(0, 1, 2) X(1, 1, 4) X(2, 2, 1) X(3, 2, 2) X(4, 2, 4)
-#define DRN_NK_NCFG 5
-#define DRN_NK_CFG0 200  // configuration id of NK config 0 (DrnConvFwdArgs::cfg)
+struct NkCfg {
+  int mi, mj;
+};
+constexpr NkCfg kNkCfg[] = {{1, 2}, {1, 4}, {2, 1}, {2, 2}, {2, 4}};
+constexpr int kNkNumCfg = sizeof(kNkCfg) / sizeof(kNkCfg[0]);
+constexpr int kNkCfg0 = 200;  // configuration id of NK config 0 (DrnConvFwdArgs::cfg)
 
 template <int MI, int MJ, bool PRO, int KMAX>
 static int launch_conv_nk_k(DrnConvFwdArgs* a, hipStream_t stream) {
@@ -912,8 +923,9 @@ static int launch_conv_nk_k(DrnConvFwdArgs* a, hipStream_t stream) {
   return (int)hipGetLastError();
 }
 
-template <int MI, int MJ, bool PRO>
+template <int ID, bool PRO>
 static int launch_conv_nk_p(DrnConvFwdArgs* a, hipStream_t stream) {
+  constexpr int MI = kNkCfg[ID].mi, MJ = kNkCfg[ID].mj;
   const int ksteps = (a->R * a->S * a->C + 31) / 32;
   if (ksteps <= 2) return launch_conv_nk_k<MI, MJ, PRO, 2>(a, stream);
   if (ksteps <= 5) return launch_conv_nk_k<MI, MJ, PRO, 5>(a, stream);
@@ -921,37 +933,21 @@ static int launch_conv_nk_p(DrnConvFwdArgs* a, hipStream_t stream) {
   return (int)hipErrorInvalidValue;
 }
 
-static int nk_cfg_mi(int id) {
-  switch (id) {
-#define DRN_X(id, mi, mj) \
-  case id:                \
-    return mi;
-    DRN_NK_CONFIGS(DRN_X)
-#undef DRN_X
-    default:
-      return 0;
-  }
-}
-
-static int nk_cfg_mj(int id) {
-  switch (id) {
-#define DRN_X(id, mi, mj) \
-  case id:                \
-    return mj;
-    DRN_NK_CONFIGS(DRN_X)
-#undef DRN_X
-    default:
-      return 1;
-  }
+typedef int (*NkLaunchFn)(DrnConvFwdArgs*, hipStream_t);
+template <int... ID>  // [id][fused BN prologue]
+constexpr std::array<std::array<NkLaunchFn, 2>, sizeof...(ID)> nk_launch_table(std::integer_sequence<int, ID...>) {
+  return {{{{&launch_conv_nk_p<ID, false>, &launch_conv_nk_p<ID, true>}}...}};
 }
 
 static int launch_conv_nk(int id, DrnConvFwdArgs* a, hipStream_t stream) {
-  const int mi = nk_cfg_mi(id);
-  if (mi == 0 || a->K != 16 * mi || a->dil != 1 || a->ksplit > 1 || a->sk_blocks > 0 ||
+  static constexpr auto table = nk_launch_table(std::make_integer_sequence<int, kNkNumCfg>{});
+  if (id < 0 || id >= kNkNumCfg) return (int)hipErrorInvalidValue;
+  const int mi = kNkCfg[id].mi, bp = 16 * 4 * kNkCfg[id].mj;
+  if (a->K != 16 * mi || a->dil != 1 || a->ksplit > 1 || a->sk_blocks > 0 ||
       a->C < 8 || (a->C & (a->C - 1)) != 0 || (a->R * a->S * a->C + 31) / 32 > 9)
     return (int)hipErrorInvalidValue;
-  if (a->in_fin.stats != nullptr && (a->N * a->P * a->Q + 16 * 4 * nk_cfg_mj(id) - 1) / (16 * 4 * nk_cfg_mj(id)) >
-                                         cfin_max_blocks()) {  // big grid: the finalize as its own launch
+  if (a->in_fin.stats != nullptr && (a->N * a->P * a->Q + bp - 1) / bp > cfin_max_blocks()) {
+    // big grid: the finalize as its own launch
     if (a->in_fin.publish) {
       const int rc = drn_bn_fin_fwd_launch(&a->in_fin, stream);
       if (rc) return rc;
@@ -962,16 +958,7 @@ static int launch_conv_nk(int id, DrnConvFwdArgs* a, hipStream_t stream) {
     a->tiles_p = b.tiles_p;
     return rc;
   }
-  const bool pro = a->in_scale != nullptr;
-  switch (id) {
-#define DRN_X(id, mi, mj) \
-  case id:                \
-    return pro ? launch_conv_nk_p<mi, mj, true>(a, stream) : launch_conv_nk_p<mi, mj, false>(a, stream);
-    DRN_NK_CONFIGS(DRN_X)
-#undef DRN_X
-    default:
-      return (int)hipErrorInvalidValue;
-  }
+  return table[id][a->in_scale != nullptr](a, stream);
 }
 
 // partial-tile slots a stream-K launch needs per tile: the most workgroup ranges one tile's T
@@ -997,9 +984,76 @@ static int cfin_max_blocks() { return 2048; }
 // channels x 64 B = 51 MB, 8 dependent channel rounds per thread)
 static long cfin_max_work() { return 1L << 19; }
 
-template <int BP, int BC, int WAVES_P, int NS, int NW, bool PF, int BK, bool PRO, bool SROW = false, int NH = 1,
-          bool KS = false, bool IL = false>
-static int launch_conv_glds_pf(DrnConvFwdArgs* a, const void* zero, hipStream_t stream) {
+// Tile configurations of the LDS-DMA kernel, indexed by the DRN conv config id (the ids are
+// stored in the shipped kernel database: append, never renumber). 25-30: 8-wave big tiles with
+// 32-deep stages and 3-4 stages in flight (one workgroup per CU): a 128 x 128 tile needs 64 B per
+// MFMA cycle from L2 -- the per-CU L2 read rate -- 256 x 256 half that. il = the next stage's
+// LDS-DMA pieces interleaved with the MFMAs (31-37 = il twins of the most used configs).
+// ks = split-K / stream-K capable (DrnConvFwdArgs::ksplit > 1 / sk_blocks > 0, last-arriver
+// epilogue). nh = channel slices of the epilogue (> 1: sliced, no operand prefetch).
+struct GldsCfg {
+  int bp, bc, waves_p, ns, nw, bk, nh;
+  bool il, ks;
+};
+constexpr GldsCfg kGldsCfg[] = {
+    {128, 128, 2, 2, 4, 64, 1, false, true},   // 0
+    {128, 128, 2, 3, 4, 64, 1, false, false},  // 1
+    {128, 128, 2, 4, 4, 64, 1, false, false},  // 2
+    {256, 64, 4, 2, 4, 64, 1, false, false},   // 3
+    {256, 64, 4, 3, 4, 64, 1, false, false},   // 4
+    {128, 64, 2, 3, 4, 64, 1, false, false},   // 5
+    {64, 128, 1, 3, 4, 64, 1, false, false},   // 6
+    {64, 64, 2, 4, 4, 64, 1, false, false},    // 7
+    {256, 128, 4, 2, 8, 64, 1, false, false},  // 8
+    {256, 128, 4, 3, 8, 64, 1, false, false},  // 9
+    {128, 256, 2, 2, 8, 64, 1, false, false},  // 10
+    {128, 256, 2, 3, 8, 64, 1, false, false},  // 11
+    {128, 64, 2, 2, 4, 64, 1, false, false},   // 12
+    {64, 128, 1, 2, 4, 64, 1, false, true},    // 13
+    {64, 64, 2, 2, 4, 64, 1, false, false},    // 14
+    {64, 256, 1, 2, 4, 64, 1, false, false},   // 15
+    {32, 128, 1, 2, 4, 64, 1, false, false},   // 16
+    {128, 128, 2, 4, 4, 32, 1, false, false},  // 17
+    {64, 128, 1, 4, 4, 32, 1, false, false},   // 18
+    {128, 64, 2, 4, 4, 32, 1, false, false},   // 19
+    {128, 128, 2, 3, 4, 32, 1, false, false},  // 20
+    {64, 128, 1, 3, 4, 32, 1, false, false},   // 21
+    {256, 64, 4, 4, 4, 32, 1, false, false},   // 22
+    {256, 32, 4, 2, 4, 64, 1, false, false},   // 23
+    {128, 32, 4, 3, 4, 64, 1, false, false},   // 24
+    {256, 256, 4, 4, 8, 32, 2, false, true},   // 25
+    {256, 256, 4, 2, 8, 64, 2, false, false},  // 26
+    {256, 128, 4, 5, 8, 32, 1, false, false},  // 27
+    {128, 256, 2, 5, 8, 32, 1, false, false},  // 28
+    {256, 256, 2, 4, 8, 32, 2, false, false},  // 29
+    {256, 128, 2, 4, 8, 32, 1, false, false},  // 30
+    {128, 128, 2, 2, 4, 64, 1, true, true},    // 31
+    {64, 128, 1, 2, 4, 64, 1, true, true},     // 32
+    {256, 256, 4, 4, 8, 32, 2, true, true},    // 33
+    {256, 128, 4, 2, 8, 64, 1, true, false},   // 34
+    {64, 256, 1, 2, 4, 64, 1, true, false},    // 35
+    {128, 64, 2, 4, 4, 32, 1, true, false},    // 36
+    {64, 128, 1, 3, 4, 32, 1, true, false},    // 37
+};
+constexpr int kGldsNumCfg = sizeof(kGldsCfg) / sizeof(kGldsCfg[0]);
+
+// The variants (flag sets without kIL, which the configuration fixes) a configuration is built
+// in: the sliced-epilogue big tiles (nh > 1) never prefetch epilogue operands, row-staged narrow
+// inputs only on one-slice plain-issue 64-deep configurations and never split, split-K /
+// stream-K only on the split-capable configurations.
+constexpr bool glds_variant_ok(const GldsCfg& c, unsigned f) {
+  if ((f & kPF) && c.nh > 1) return false;
+  if ((f & kSROW) && (c.nh > 1 || c.bk != 64 || c.il || (f & kKS))) return false;
+  if ((f & kKS) && !c.ks) return false;
+  return true;
+}
+
+// One instantiation: configuration CFG with the variant flags F (kIL included).
+template <int CFG, unsigned F>
+static int launch_conv_glds_f(DrnConvFwdArgs* a, const void* zero, hipStream_t stream) {
+  constexpr GldsCfg c = kGldsCfg[CFG];
+  constexpr int BP = c.bp, BC = c.bc, WAVES_P = c.waves_p, NS = c.ns, NW = c.nw, BK = c.bk, NH = c.nh;
+  constexpr bool PRO = F & kPRO, KS = F & kKS;
   const int T = a->C == 4 ? (a->R + 1) / 2 : a->C == 8 || a->C == 16 ? a->R : (a->R * a->S * a->C) / BK;  // k-stages
                                                           // (SROW: filter rows; packed stem: row pairs)
   const int LDS0 = (T < NS ? T : NS) * (BC + BP) * BK * 2;  // stage slots actually used
@@ -1007,7 +1061,7 @@ static int launch_conv_glds_pf(DrnConvFwdArgs* a, const void* zero, hipStream_t 
   const int LDS = lds_main > BP * BC * 4 / NH ? lds_main : BP * BC * 4 / NH;  // epilogue staging slice
   if (LDS > 160 * 1024) return (int)hipErrorInvalidValue;
   static bool attr_set = false;
-  auto kern = conv_fwd_glds_kernel<BP, BC, WAVES_P, NS, NW, PF, BK, PRO, SROW, NH, KS, IL>;
+  auto kern = conv_fwd_glds_kernel<BP, BC, WAVES_P, NS, NW, BK, NH, F>;
   if (!attr_set) {
     hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr_set = true;
@@ -1021,7 +1075,7 @@ static int launch_conv_glds_pf(DrnConvFwdArgs* a, const void* zero, hipStream_t 
       if (a->ks_ws == nullptr || a->ks_tickets == nullptr) return (int)hipErrorInvalidValue;
       const int need = sk_slots(tiles_p * tiles_c, T, a->sk_blocks);
       if (need == 0 || need > a->ksplit) return (int)hipErrorInvalidValue;
-      auto skern = conv_fwd_glds_sk_kernel<BP, BC, WAVES_P, NS, NW, BK, PRO, NH, IL>;
+      auto skern = conv_fwd_glds_sk_kernel<BP, BC, WAVES_P, NS, NW, BK, NH, F & ~kPF>;
       static bool sk_attr_set = false;
       if (!sk_attr_set) {
         hipFuncSetAttribute(reinterpret_cast<const void*>(skern), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1051,155 +1105,45 @@ static int launch_conv_glds_pf(DrnConvFwdArgs* a, const void* zero, hipStream_t 
   return (int)hipGetLastError();
 }
 
-template <int BP, int BC, int WAVES_P, int NS, int NW, int BK, bool IL>
-static int launch_conv_glds_nh1(DrnConvFwdArgs* a, const void* zero, hipStream_t stream);
-
-// split-K launch (a->ksplit > 1): plain / fused-BN-prologue inputs only
-template <int BP, int BC, int WAVES_P, int NS, int NW, int BK, int NH, bool IL>
-static int launch_conv_glds_ks(DrnConvFwdArgs* a, const void* zero, hipStream_t stream) {
-  if (a->C == 4 || a->C == 8 || a->C == 16 || a->C % BK) return (int)hipErrorInvalidValue;
-  // epilogue operands: prefetched by the (NH == 1) kernels that keep them in registers
-  constexpr bool PFOK = NH == 1;
-  const bool pf = PFOK && (a->residual != nullptr || a->bn_x != nullptr);
-  if (a->in_scale != nullptr)
-    return pf ? launch_conv_glds_pf<BP, BC, WAVES_P, NS, NW, PFOK, BK, true, false, NH, true, IL>(a, zero, stream)
-              : launch_conv_glds_pf<BP, BC, WAVES_P, NS, NW, false, BK, true, false, NH, true, IL>(a, zero, stream);
-  return pf ? launch_conv_glds_pf<BP, BC, WAVES_P, NS, NW, PFOK, BK, false, false, NH, true, IL>(a, zero, stream)
-            : launch_conv_glds_pf<BP, BC, WAVES_P, NS, NW, false, BK, false, false, NH, true, IL>(a, zero, stream);
-}
-
-// epilogue operands (residual / BN-backward input) are prefetched only when present
-template <int BP, int BC, int WAVES_P, int NS, int NW = 4, int BK = 64, int NH = 1, bool IL = false, bool KSOK = false>
+// The launcher of configuration CFG: derives the variant flags of this launch once, refuses what
+// the configuration does not cover, and maps the flags to the instantiation.
+template <int CFG>
 static int launch_conv_glds(DrnConvFwdArgs* a, const void* zero, hipStream_t stream) {
-  if (a->ksplit > 1 || a->sk_blocks > 0) {
-    if constexpr (KSOK) return launch_conv_glds_ks<BP, BC, WAVES_P, NS, NW, BK, NH, IL>(a, zero, stream);
+  constexpr GldsCfg c = kGldsCfg[CFG];
+  const bool split = a->ksplit > 1 || a->sk_blocks > 0;                 // split-K / stream-K
+  const bool srow = a->C == 4 || a->C == 8 || a->C == 16;               // row-staged narrow input (stem, CIFAR)
+  // epilogue operands (residual / BN-backward input) are prefetched only when present, by the
+  // one-slice kernels that keep them in registers
+  const bool pf = c.nh == 1 && (a->residual != nullptr || a->bn_x != nullptr);
+  const unsigned f = (pf ? kPF : 0u) | (a->in_scale != nullptr ? kPRO : 0u) | (srow ? kSROW : 0u) | (split ? kKS : 0u);
+  if (srow) {
+    if (a->S * a->C > (a->C == 4 ? 32 : 64)) return (int)hipErrorInvalidValue;
+    if (a->C == 4 && (a->S % 2 || a->in_scale != nullptr)) return (int)hipErrorInvalidValue;
+  } else if (a->C % c.bk) {
     return (int)hipErrorInvalidValue;
   }
-  if constexpr (NH > 1) {  // big tiles: plain / fused-BN-prologue input, sliced epilogue, no prefetch
-    if (a->C == 4 || a->C == 8 || a->C == 16 || a->C % BK) return (int)hipErrorInvalidValue;
-    if (a->in_scale != nullptr)
-      return launch_conv_glds_pf<BP, BC, WAVES_P, NS, NW, false, BK, true, false, NH, false, IL>(a, zero, stream);
-    return launch_conv_glds_pf<BP, BC, WAVES_P, NS, NW, false, BK, false, false, NH, false, IL>(a, zero, stream);
-  } else {
-    return launch_conv_glds_nh1<BP, BC, WAVES_P, NS, NW, BK, IL>(a, zero, stream);
+  switch (f) {
+#define DRN_VARIANT(V)                                                                                         \
+  case V:                                                                                                      \
+    if constexpr (glds_variant_ok(c, V)) return launch_conv_glds_f<CFG, (V) | (c.il ? kIL : 0u)>(a, zero, stream); \
+    break;
+    DRN_VARIANT(0u) DRN_VARIANT(kPF) DRN_VARIANT(kPRO) DRN_VARIANT(kPF | kPRO)
+    DRN_VARIANT(kSROW) DRN_VARIANT(kSROW | kPF) DRN_VARIANT(kSROW | kPRO) DRN_VARIANT(kSROW | kPF | kPRO)
+    DRN_VARIANT(kKS) DRN_VARIANT(kKS | kPF) DRN_VARIANT(kKS | kPRO) DRN_VARIANT(kKS | kPF | kPRO)
+#undef DRN_VARIANT
   }
+  return (int)hipErrorInvalidValue;  // a variant this configuration is not built in
 }
 
-template <int BP, int BC, int WAVES_P, int NS, int NW, int BK, bool IL>
-static int launch_conv_glds_nh1(DrnConvFwdArgs* a, const void* zero, hipStream_t stream) {
-  const bool pf = a->residual != nullptr || a->bn_x != nullptr;
-  if (a->C == 4 || a->C == 8 || a->C == 16) {  // row-staged narrow conv (the stem, the CIFAR first stage)
-    if constexpr (BK == 64 && !IL) {
-      if (a->S * a->C > (a->C == 4 ? 32 : 64)) return (int)hipErrorInvalidValue;
-      if (a->C == 4 && (a->S % 2 || a->in_scale != nullptr)) return (int)hipErrorInvalidValue;
-      if (a->in_scale != nullptr)
-        return pf ? launch_conv_glds_pf<BP, BC, WAVES_P, NS, NW, true, BK, true, true>(a, zero, stream)
-                  : launch_conv_glds_pf<BP, BC, WAVES_P, NS, NW, false, BK, true, true>(a, zero, stream);
-      return pf ? launch_conv_glds_pf<BP, BC, WAVES_P, NS, NW, true, BK, false, true>(a, zero, stream)
-                : launch_conv_glds_pf<BP, BC, WAVES_P, NS, NW, false, BK, false, true>(a, zero, stream);
-    }
-    return (int)hipErrorInvalidValue;
-  }
-  if (a->C % BK) return (int)hipErrorInvalidValue;
-  if (a->in_scale != nullptr)
-    return pf ? launch_conv_glds_pf<BP, BC, WAVES_P, NS, NW, true, BK, true, false, 1, false, IL>(a, zero, stream)
-              : launch_conv_glds_pf<BP, BC, WAVES_P, NS, NW, false, BK, true, false, 1, false, IL>(a, zero, stream);
-  return pf ? launch_conv_glds_pf<BP, BC, WAVES_P, NS, NW, true, BK, false, false, 1, false, IL>(a, zero, stream)
-            : launch_conv_glds_pf<BP, BC, WAVES_P, NS, NW, false, BK, false, false, 1, false, IL>(a, zero, stream);
+typedef int (*GldsLaunchFn)(DrnConvFwdArgs*, const void*, hipStream_t);
+template <int... CFG>
+constexpr std::array<GldsLaunchFn, sizeof...(CFG)> glds_launch_table(std::integer_sequence<int, CFG...>) {
+  return {{&launch_conv_glds<CFG>...}};
 }
-
-// Tile configurations of the LDS-DMA kernel (index = DRN conv config id, also used by the
-// host-side autotuner): {BP, BC, WAVES_P, NS, NW, BK, NH, IL, KS}. 25-30: 8-wave big tiles with
-// 32-deep stages and 3-4 stages in flight (one workgroup per CU): a 128 x 128 tile needs 64 B per
-// MFMA cycle from L2 -- the per-CU L2 read rate -- 256 x 256 half that. IL = the next stage's
-// LDS-DMA pieces interleaved with the MFMAs (31-37 = IL twins of the most used configs).
-// KS = split-K capable (DrnConvFwdArgs::ksplit > 1, last-arriver epilogue).
-#define DRN_GLDS_CONFIGS(X)                 \
-  X(0, 128, 128, 2, 2, 4, 64, 1, false, true)  \
-  X(1, 128, 128, 2, 3, 4, 64, 1, false, false) \
-  X(2, 128, 128, 2, 4, 4, 64, 1, false, false) \
-  X(3, 256, 64, 4, 2, 4, 64, 1, false, false)  \
-  X(4, 256, 64, 4, 3, 4, 64, 1, false, false)  \
-  X(5, 128, 64, 2, 3, 4, 64, 1, false, false)  \
-  X(6, 64, 128, 1, 3, 4, 64, 1, false, false)  \
-  X(7, 64, 64, 2, 4, 4, 64, 1, false, false)   \
-  X(8, 256, 128, 4, 2, 8, 64, 1, false, false) \
-  X(9, 256, 128, 4, 3, 8, 64, 1, false, false) \
-  X(10, 128, 256, 2, 2, 8, 64, 1, false, false) \
-  X(11, 128, 256, 2, 3, 8, 64, 1, false, false) \
-  X(12, 128, 64, 2, 2, 4, 64, 1, false, false) \
-  X(13, 64, 128, 1, 2, 4, 64, 1, false, true)  \
-  X(14, 64, 64, 2, 2, 4, 64, 1, false, false)  \
-  X(15, 64, 256, 1, 2, 4, 64, 1, false, false) \
-  X(16, 32, 128, 1, 2, 4, 64, 1, false, false) \
-  X(17, 128, 128, 2, 4, 4, 32, 1, false, false) \
-  X(18, 64, 128, 1, 4, 4, 32, 1, false, false) \
-  X(19, 128, 64, 2, 4, 4, 32, 1, false, false) \
-  X(20, 128, 128, 2, 3, 4, 32, 1, false, false) \
-  X(21, 64, 128, 1, 3, 4, 32, 1, false, false) \
-  X(22, 256, 64, 4, 4, 4, 32, 1, false, false) \
-  X(23, 256, 32, 4, 2, 4, 64, 1, false, false) \
-  X(24, 128, 32, 4, 3, 4, 64, 1, false, false) \
-  X(25, 256, 256, 4, 4, 8, 32, 2, false, true) \
-  X(26, 256, 256, 4, 2, 8, 64, 2, false, false) \
-  X(27, 256, 128, 4, 5, 8, 32, 1, false, false) \
-  X(28, 128, 256, 2, 5, 8, 32, 1, false, false) \
-  X(29, 256, 256, 2, 4, 8, 32, 2, false, false) \
-  X(30, 256, 128, 2, 4, 8, 32, 1, false, false) \
-  X(31, 128, 128, 2, 2, 4, 64, 1, true, true)   \
-  X(32, 64, 128, 1, 2, 4, 64, 1, true, true)    \
-  X(33, 256, 256, 4, 4, 8, 32, 2, true, true)   \
-  X(34, 256, 128, 4, 2, 8, 64, 1, true, false)  \
-  X(35, 64, 256, 1, 2, 4, 64, 1, true, false)   \
-  X(36, 128, 64, 2, 4, 4, 32, 1, true, false)   \
-  X(37, 64, 128, 1, 3, 4, 32, 1, true, false)
 
 static int launch_glds_cfg(int cfg, DrnConvFwdArgs* a, const void* zero, hipStream_t s) {
-  switch (cfg) {
-#define DRN_X(id, bp, bc, wpv, ns, nw, bk, nh, il, ks) \
-  case id:                                             \
-    return launch_conv_glds<bp, bc, wpv, ns, nw, bk, nh, il, ks>(a, zero, s);
-    DRN_GLDS_CONFIGS(DRN_X)
-#undef DRN_X
-    default:
-      return (int)hipErrorInvalidValue;
-  }
-}
-
-static int glds_cfg_bp(int cfg) {
-  switch (cfg) {
-#define DRN_X(id, bp, bc, wpv, ns, nw, bk, nh, il, ks) \
-  case id:                                             \
-    return bp;
-    DRN_GLDS_CONFIGS(DRN_X)
-#undef DRN_X
-    default:
-      return 0;
-  }
-}
-
-static int glds_cfg_bk(int cfg) {
-  switch (cfg) {
-#define DRN_X(id, bp, bc, wpv, ns, nw, bk, nh, il, ks) \
-  case id:                                             \
-    return ks ? bk : 0;
-    DRN_GLDS_CONFIGS(DRN_X)
-#undef DRN_X
-    default:
-      return 0;
-  }
-}
-
-static int glds_cfg_bc(int cfg) {
-  switch (cfg) {
-#define DRN_X(id, bp, bc, wpv, ns, nw, bk, nh, il, ks) \
-  case id:                                             \
-    return bc;
-    DRN_GLDS_CONFIGS(DRN_X)
-#undef DRN_X
-    default:
-      return 0;
-  }
+  static constexpr auto table = glds_launch_table(std::make_integer_sequence<int, kGldsNumCfg>{});
+  return cfg >= 0 && cfg < kGldsNumCfg ? table[cfg](a, zero, s) : (int)hipErrorInvalidValue;
 }
 
 // Default choice when the host did not autotune (measured on the ResNet-50 layer set): the
@@ -1251,8 +1195,6 @@ DRN_API int drn_conv_fwd_tiles_p(int M, int K) {
 
 DRN_API int drn_conv_fwd(DrnConvFwdArgs* a, hipStream_t s);
 
-#define DRN_GLDS_NCFG 38
-
 // Whether the LDS-DMA kernel family supports this convolution.
 DRN_API int drn_conv_glds_ok(const DrnConvFwdArgs* a) {
   if (a->C == 4)  // packed stem (stem.hip): tap pairs of 4 channels, two filter rows per stage
@@ -1269,17 +1211,18 @@ DRN_API int drn_conv_glds_ok(const DrnConvFwdArgs* a) {
 DRN_API int drn_conv_fwd2(DrnConvFwdArgs* a, const void* zero, hipStream_t s) {
   if ((a->C % 8) != 0 && a->C != 4) return (int)hipErrorInvalidValue;
   if ((a->K % 8) != 0) return (int)hipErrorInvalidValue;
-  if (a->C == 4 && (!drn_conv_glds_ok(a) || zero == nullptr || a->cfg == 100 || a->cfg >= DRN_GLDS_NCFG))
+  if (a->C == 4 && (!drn_conv_glds_ok(a) || zero == nullptr || a->cfg == 100 || a->cfg >= drn::kGldsNumCfg))
     return (int)hipErrorInvalidValue;  // the packed stem exists on the one-tile LDS-DMA path only
   if (a->fin_cnt != nullptr && (a->stats == nullptr || a->K > 64 * 64)) return (int)hipErrorInvalidValue;
   if (a->in_fin.stats != nullptr &&
       (a->in_scale == nullptr || a->in_fin.C != a->C || a->in_fin.G < 1 || a->in_fin.G > DRN_BN_FIN_GMAX))
     return (int)hipErrorInvalidValue;
   if ((a->ksplit > 1 || a->sk_blocks > 0) &&
-      (a->cfg < 0 || a->cfg >= DRN_GLDS_NCFG || !drn_conv_glds_ok(a) || zero == nullptr))
+      (a->cfg < 0 || a->cfg >= drn::kGldsNumCfg || !drn_conv_glds_ok(a) || zero == nullptr))
     return (int)hipErrorInvalidValue;  // split-K: explicit split-capable LDS-DMA configurations only
-  if (a->cfg >= DRN_NK_CFG0 && a->cfg < DRN_NK_CFG0 + DRN_NK_NCFG) return drn::launch_conv_nk(a->cfg - DRN_NK_CFG0, a, s);
-  if (a->cfg >= DRN_GLDS_NCFG && a->cfg != 100) return (int)hipErrorInvalidValue;
+  if (a->cfg >= drn::kNkCfg0 && a->cfg < drn::kNkCfg0 + drn::kNkNumCfg)
+    return drn::launch_conv_nk(a->cfg - drn::kNkCfg0, a, s);
+  if (a->cfg >= drn::kGldsNumCfg && a->cfg != 100) return (int)hipErrorInvalidValue;
   if (drn_conv_glds_ok(a) && zero != nullptr && a->cfg != 100)
     return drn::launch_glds_cfg(a->cfg >= 0 ? a->cfg : drn::glds_default_cfg(a), a, zero, s);
   if (a->in_fin.stats != nullptr) {
@@ -1301,23 +1244,34 @@ DRN_API int drn_conv_trace_set(unsigned long long* buf) {
 }
 #endif
 
-DRN_API int drn_conv_glds_cfg_bp(int cfg) { return drn::glds_cfg_bp(cfg); }
-DRN_API int drn_conv_glds_cfg_bc(int cfg) { return drn::glds_cfg_bc(cfg); }
-// k depth of a split-capable configuration's stages (0: not split-K / stream-K capable)
-DRN_API int drn_conv_glds_cfg_bk(int cfg) { return drn::glds_cfg_bk(cfg); }
+// The properties of configuration id cfg (DrnConvCfgInfo, drn_conv.h): an LDS-DMA tile
+// configuration or a narrow-output one; nonzero for an id that is neither.
+DRN_API int drn_conv_cfg_info(int cfg, DrnConvCfgInfo* o) {
+  if (cfg >= 0 && cfg < drn::kGldsNumCfg) {
+    const drn::GldsCfg& c = drn::kGldsCfg[cfg];
+    *o = DrnConvCfgInfo{0, c.bp, c.bc, c.waves_p, c.ns, c.nw, c.bk, c.nh, c.il, c.ks};
+    return 0;
+  }
+  if (cfg >= drn::kNkCfg0 && cfg < drn::kNkCfg0 + drn::kNkNumCfg) {
+    const drn::NkCfg& c = drn::kNkCfg[cfg - drn::kNkCfg0];
+    *o = DrnConvCfgInfo{1, 16 * 4 * c.mj, 16 * c.mi, 4, 0, 4, 32, 1, 0, 0};
+    return 0;
+  }
+  return (int)hipErrorInvalidValue;
+}
 // partial slots per tile a stream-K launch of split-capable config cfg with G workgroups needs
 // (0: not split-capable, or more workgroups than tile x k-stage units)
 DRN_API int drn_conv_sk_slots_cfg(const DrnConvFwdArgs* a, int cfg, int G) {
-  const int bk = drn::glds_cfg_bk(cfg);
-  if (bk == 0 || (a->R * a->S * a->C) % bk) return 0;
+  if (cfg < 0 || cfg >= drn::kGldsNumCfg || !drn::kGldsCfg[cfg].ks) return 0;
+  const drn::GldsCfg& c = drn::kGldsCfg[cfg];
+  if ((a->R * a->S * a->C) % c.bk) return 0;
   const int M = a->N * a->P * a->Q;
-  const int bp = drn::glds_cfg_bp(cfg), bc = drn::glds_cfg_bc(cfg);
-  return drn::sk_slots(((M + bp - 1) / bp) * ((a->K + bc - 1) / bc), (a->R * a->S * a->C) / bk, G);
+  return drn::sk_slots(((M + c.bp - 1) / c.bp) * ((a->K + c.bc - 1) / c.bc), (a->R * a->S * a->C) / c.bk, G);
 }
-// narrow-output (K = 16 / 32) register-operand kernels: configuration ids DRN_NK_CFG0 + i
-DRN_API int drn_conv_nk_num_cfgs() { return DRN_NK_NCFG; }
-DRN_API int drn_conv_nk_cfg0() { return DRN_NK_CFG0; }
-DRN_API int drn_conv_glds_num_cfgs() { return DRN_GLDS_NCFG; }
+// narrow-output (K = 16 / 32) register-operand kernels: configuration ids drn::kNkCfg0 + i
+DRN_API int drn_conv_nk_num_cfgs() { return drn::kNkNumCfg; }
+DRN_API int drn_conv_nk_cfg0() { return drn::kNkCfg0; }
+DRN_API int drn_conv_glds_num_cfgs() { return drn::kGldsNumCfg; }
 DRN_API int drn_conv_glds_default_cfg(const DrnConvFwdArgs* a) { return drn::glds_default_cfg(a); }
 
 DRN_API int drn_conv_fwd(DrnConvFwdArgs* a, hipStream_t s) {

@@ -22,7 +22,14 @@
 // drn_splitk_reduce (no float atomics: bitwise-reproducible weight gradients).
 #include "drn_common.h"
 #include "drn_conv.h"
+#include "drn_conv_epi.h"
 #include <stdlib.h>
+
+#ifdef DRN_ISO_NOLOOP  // bound isolation (scripts/conv_bound_iso.py): prologue + epilogue only
+#define ISO_T(T) 0
+#else
+#define ISO_T(T) (T)
+#endif
 
 namespace drn {
 
@@ -31,11 +38,6 @@ namespace drn {
 // end} in s_memrealtime ticks (100 MHz) + HW_ID / XCC_ID, at the workgroup's linear launch index.
 #ifdef DRN_CONV_TRACE
 __device__ unsigned long long* g_wgrad_trace = nullptr;
-__device__ __forceinline__ unsigned long long wg_realtime() {
-  unsigned long long t;
-  asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t));
-  return t;
-}
 #endif
 
 __device__ __forceinline__ uint32_t fdiv(uint32_t n, const DrnFastDiv& f) { return drn_fdiv(n, f); }
@@ -307,14 +309,6 @@ static int dispatch_wgrad(DrnConvWgradArgs* a, hipStream_t s) {
 // (tap, channel) chunk once. Out-of-image taps, pixels past the split and channels past K
 // read the zero page.
 // ---------------------------------------------------------------------------------------
-typedef __attribute__((address_space(3))) void wg_lds_void;
-typedef __attribute__((address_space(1))) const void wg_gbl_void;
-
-template <int N>
-__device__ __forceinline__ void wg_wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
 template <int V>
 struct drn_int_c {
   static constexpr int value = V;
@@ -386,7 +380,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_glds_kernel(DrnConvWgradArgs a
 #ifdef DRN_CONV_TRACE
   unsigned long long* const trace = g_wgrad_trace;
   unsigned long long t_start = 0;
-  if (trace != nullptr) t_start = wg_realtime();
+  if (trace != nullptr) t_start = drn_realtime();
 #endif
 
   // (wave index made provably wave-uniform: LDS-DMA destinations then stay in SGPRs / M0)
@@ -513,7 +507,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_glds_kernel(DrnConvWgradArgs a
       const uint32_t bit = 1u << (slot * IA + i);
       okm = ok ? (okm | bit) : (okm & ~bit);
     }
-    __builtin_amdgcn_global_load_lds((wg_gbl_void*)src, (wg_lds_void*)(st + r0 * WA), 16, 0, 0);
+    DRN_GLDS16(src, st + r0 * WA);
     am[i] += BP;
     ww[i] += d_w;
     hh[i] += d_h;
@@ -536,8 +530,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_glds_kernel(DrnConvWgradArgs a
       if (full && a_full) {
 #pragma unroll
         for (int i = 0; i < IA; ++i)
-          __builtin_amdgcn_global_load_lds((wg_gbl_void*)(xs + offA[i]), (wg_lds_void*)(st + RIA * (wave + 4 * i) * WA),
-                                           16, 0, 0);
+          DRN_GLDS16(xs + offA[i], st + RIA * (wave + 4 * i) * WA);
         if constexpr (PRO) okm |= ((1u << IA) - 1u) << (slot * IA);
       } else {
 #pragma unroll
@@ -547,8 +540,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_glds_kernel(DrnConvWgradArgs a
             const uint32_t bit = 1u << (slot * IA + i);
             okm = ok ? (okm | bit) : (okm & ~bit);
           }
-          __builtin_amdgcn_global_load_lds((wg_gbl_void*)(ok ? (const void*)(xs + offA[i]) : zero),
-                                           (wg_lds_void*)(st + RIA * (wave + 4 * i) * WA), 16, 0, 0);
+          DRN_GLDS16(ok ? (const void*)(xs + offA[i]) : zero, st + RIA * (wave + 4 * i) * WA);
         }
       }
     }
@@ -558,15 +550,13 @@ __global__ __launch_bounds__(256) void conv_wgrad_glds_kernel(DrnConvWgradArgs a
     if (full && b_full) {
 #pragma unroll
       for (int i = 0; i < IB; ++i)
-        __builtin_amdgcn_global_load_lds((wg_gbl_void*)(ds + offB[i]), (wg_lds_void*)(st + A_BYTES + RIB * (wave + 4 * i) * WB),
-                                         16, 0, 0);
+        DRN_GLDS16(ds + offB[i], st + A_BYTES + RIB * (wave + 4 * i) * WB);
     } else {
 #pragma unroll
       for (int i = 0; i < IB; ++i) {
         const int r0 = RIB * (wave + 4 * i);
         const bool ok = cvalid && mstep + r0 + brow < mend;
-        __builtin_amdgcn_global_load_lds((wg_gbl_void*)(ok ? (const void*)(ds + offB[i]) : zero),
-                                         (wg_lds_void*)(st + A_BYTES + r0 * WB), 16, 0, 0);
+        DRN_GLDS16(ok ? (const void*)(ds + offB[i]) : zero, st + A_BYTES + r0 * WB);
       }
     }
   };
@@ -582,8 +572,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_glds_kernel(DrnConvWgradArgs a
     const int r0 = RIB * (wave + 4 * i);
     const int m = mstep + r0 + brow;
     const bool ok = cvalid && m < mend;
-    __builtin_amdgcn_global_load_lds((wg_gbl_void*)(ok ? (const void*)(dyg + (uint32_t)__mul24(m, a.K)) : zero),
-                                     (wg_lds_void*)(st + A_BYTES + r0 * WB), 16, 0, 0);
+    DRN_GLDS16(ok ? (const void*)(dyg + (uint32_t)__mul24(m, a.K)) : zero, st + A_BYTES + r0 * WB);
   };
 
 
@@ -606,13 +595,15 @@ __global__ __launch_bounds__(256) void conv_wgrad_glds_kernel(DrnConvWgradArgs a
 #pragma unroll
   for (int j = 0; j < MJ; ++j) b_lane[j] = (uint32_t)swz_off<WB>(8 * g + q4, wc * WCO + 16 * j + 4 * p4);
 
+#ifndef DRN_ISO_NOLOAD  // bound isolation: no LDS-DMA (stages keep whatever the LDS held)
 #pragma unroll
   for (int s = 0; s < D; ++s)
     if (s < T) issue(s, mbeg + s * BP);
+#endif
 
-  for (int t = 0; t < T; ++t) {
-    if (t + D - 1 < T) wg_wait_vmcnt<G * (D - 1)>();
-    else wg_wait_vmcnt<0>();
+  for (int t = 0; t < ISO_T(T); ++t) {
+    if (t + D - 1 < T) wait_vmcnt<G * (D - 1)>();
+    else wait_vmcnt<0>();
     if constexpr (PRO) {
       const int slot = t % NS;
       char* sw = smem + slot * STAGE;
@@ -628,7 +619,9 @@ __global__ __launch_bounds__(256) void conv_wgrad_glds_kernel(DrnConvWgradArgs a
     }
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
+#ifndef DRN_ISO_NOLOAD
     if (!IL && t + D < T) issue((t + D) % NS, mbeg + (t + D) * BP);
+#endif
     const bool more = IL && t + D < T;
     const int nslot = (t + D) % NS, nstep = mbeg + (t + D) * BP;
     // Transposed fragment reads in inline asm: hipcc treats its ds_read_tr intrinsic as
@@ -642,6 +635,15 @@ __global__ __launch_bounds__(256) void conv_wgrad_glds_kernel(DrnConvWgradArgs a
 #pragma unroll
     for (int j = 0; j < MJ; ++j) bb[j] = cur + b_lane[j];
     s16x4v fa[KS][MI][2], fb[KS][MJ][2];
+#ifdef DRN_ISO_NOREAD  // bound isolation: operands without LDS reads
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+#pragma unroll
+      for (int i = 0; i < MI; ++i) asm volatile("" : "=v"(fa[ks][i][0]), "=v"(fa[ks][i][1]));
+#pragma unroll
+      for (int j = 0; j < MJ; ++j) asm volatile("" : "=v"(fb[ks][j][0]), "=v"(fb[ks][j][1]));
+    }
+#else
     static_for<0, KS>([&](auto KSI) {
       constexpr int ks = decltype(KSI)::value;
 #pragma unroll
@@ -655,6 +657,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_glds_kernel(DrnConvWgradArgs a
         fb[ks][j][1] = tr_read_asm<A_BYTES + (32 * ks + 4) * WB>(bb[j]);
       }
     });
+#endif
     constexpr int Q = KS * MI * MJ;
     constexpr int STEP = Q / (G + 1) > 0 ? Q / (G + 1) : 1;
 #pragma unroll
@@ -669,7 +672,11 @@ __global__ __launch_bounds__(256) void conv_wgrad_glds_kernel(DrnConvWgradArgs a
               bf16x8_t, __builtin_shufflevector(fa[ks][i][0], fa[ks][i][1], 0, 1, 2, 3, 4, 5, 6, 7));
           const bf16x8_t bfr = __builtin_bit_cast(
               bf16x8_t, __builtin_shufflevector(fb[ks][j][0], fb[ks][j][1], 0, 1, 2, 3, 4, 5, 6, 7));
+#ifdef DRN_ISO_NOMFMA  // bound isolation: loads + fragment reads only
+          asm volatile("" ::"v"(af), "v"(bfr));
+#else
           acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bfr, acc[i][j], 0, 0, 0);
+#endif
           if constexpr (IL) {
             const int q = (ks * MI + i) * MJ + j + 1;
             if (q % STEP == 0 && q / STEP <= G && more) {
@@ -691,23 +698,11 @@ __global__ __launch_bounds__(256) void conv_wgrad_glds_kernel(DrnConvWgradArgs a
 
 #ifdef DRN_CONV_TRACE
   unsigned long long t_loop = 0;
-  if (trace != nullptr) t_loop = wg_realtime();
+  if (trace != nullptr) t_loop = drn_realtime();
 #endif
   wgrad_store<MI, MJ>(a, acc, split, c0 + wc * WCO, k0 + wk * WKK, Ktot, lane);
 #ifdef DRN_CONV_TRACE
-  if (trace != nullptr) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) {
-      const unsigned hw = __builtin_amdgcn_s_getreg((31 << 11) | 4);
-      const unsigned xcc = __builtin_amdgcn_s_getreg((15 << 11) | 20);
-      unsigned long long* r = trace + 4 * (size_t)(blockIdx.x + blockIdx.y * gridDim.x);
-      r[0] = t_start;
-      r[1] = t_loop;
-      r[2] = wg_realtime();
-      r[3] = ((unsigned long long)xcc << 32) | hw;
-    }
-  }
+  conv_trace_record(trace, blockIdx.x + blockIdx.y * gridDim.x, t_start, t_loop);
 #endif
 }
 
@@ -781,16 +776,14 @@ __global__ __launch_bounds__(256) void stem_wgrad_halo_kernel(DrnConvWgradArgs a
     const int col = q0 * a.stride - a.pad_w + 2 * lane;
     const bool ok = fr < a.R && (unsigned)h < (unsigned)a.H && col >= 0 && col + 1 < a.W;
     const bf16_t* src = xg + ((size_t)(n * a.H + h) * a.W + col) * a.C;
-    __builtin_amdgcn_global_load_lds((wg_gbl_void*)(ok ? (const void*)src : zero), (wg_lds_void*)(st + wave * 1024),
-                                     16, 0, 0);
+    DRN_GLDS16(ok ? (const void*)src : zero, st + wave * 1024);
     const int m0 = np * a.Q + q0;
 #pragma unroll
     for (int i = 0; i < IB; ++i) {
       const int r0 = RIB * (wave + 4 * i);
       const bool okb = cvalid && r0 + brow < QH && m0 + r0 + brow < M;
       const bf16_t* bs = dyg + (size_t)(m0 + r0 + brow) * a.K + dc;
-      __builtin_amdgcn_global_load_lds((wg_gbl_void*)(okb ? (const void*)bs : zero),
-                                       (wg_lds_void*)(st + A_BYTES + r0 * WB), 16, 0, 0);
+      DRN_GLDS16(okb ? (const void*)bs : zero, st + A_BYTES + r0 * WB);
     }
   };
 
@@ -819,8 +812,8 @@ __global__ __launch_bounds__(256) void stem_wgrad_halo_kernel(DrnConvWgradArgs a
     if (s < T) issue(s, hbeg + s);
 
   for (int t = 0; t < T; ++t) {
-    if (t + D - 1 < T) wg_wait_vmcnt<G * (D - 1)>();
-    else wg_wait_vmcnt<0>();
+    if (t + D - 1 < T) wait_vmcnt<G * (D - 1)>();
+    else wait_vmcnt<0>();
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     if (t + D < T) issue((t + D) % NS, hbeg + t + D);

@@ -77,6 +77,19 @@ class DrnConvWgradArgs(ctypes.Structure):
     ]
 
 
+class DrnConvCfgInfo(ctypes.Structure):
+    """Mirror of csrc/include/drn_conv.h `struct DrnConvCfgInfo` (drn_conv_cfg_info)."""
+    _fields_ = [(n, c_int) for n in ("kind", "bp", "bc", "waves_p", "ns", "nw", "bk", "nh", "il", "ks")]
+
+
+def conv_cfg_info(cfg: int):
+    """The library's description of conv configuration id cfg (tile, stage depth `ns`, k per stage,
+    interleaved issue, split-capable `ks`; kind 0 = LDS-DMA, 1 = narrow-output), None for an id
+    that is neither (-1, the register-staged 100, unknown)."""
+    info = DrnConvCfgInfo()
+    return info if lib().drn_conv_cfg_info(int(cfg), ctypes.byref(info)) == 0 else None
+
+
 _SIGS = {
     "drn_version": ([], c_int),
     "drn_conv_fwd": ([ctypes.POINTER(DrnConvFwdArgs), c_p], c_int),
@@ -125,9 +138,7 @@ _SIGS = {
     "drn_p2p_step": ([c_p, c_p, c_p], c_int),
     "drn_p2p_cast": ([c_p, c_p, c_i64, c_p], c_int),
     "drn_p2p_args_size": ([], c_int),
-    "drn_conv_glds_cfg_bc": ([c_int], c_int),
-    "drn_conv_glds_cfg_bp": ([c_int], c_int),
-    "drn_conv_glds_cfg_bk": ([c_int], c_int),
+    "drn_conv_cfg_info": ([c_int, ctypes.POINTER(DrnConvCfgInfo)], c_int),
     "drn_conv_sk_slots_cfg": ([c_p, c_int, c_int], c_int),
     "drn_conv_nk_num_cfgs": ([], c_int),
     "drn_conv_nk_cfg0": ([], c_int),

@@ -212,6 +212,11 @@ class _Common:
         self.bn_bwd_apply(dy, dpool, pool_hw, x, scale, shift, fin.mean, fin.invstd, coef, add, dx, relu=relu)
 
 
+# weight-gradient pipeline ids the tuner tries by default (drn_conv_wgrad2's `ns`: 0 = register-staged,
+# 2-8 = the LDS-DMA pipelines, 9 / 10 = the packed stem's input-halo kernel); DRN_WGRAD_CANDS overrides
+WGRAD_PIPELINES = "0,2,3,4,5,6,7,8,9,10"
+
+
 class HipBackend(_Common):
     name = "hip"
     act_dtype = torch.bfloat16
@@ -341,11 +346,17 @@ class HipBackend(_Common):
 
     def _ks_need(self, a, ks: int) -> int:
         """fp32 elements of split-K workspace a launch of config a.cfg with factor ks needs."""
-        bp, bc = self.L.drn_conv_glds_cfg_bp(a.cfg), self.L.drn_conv_glds_cfg_bc(a.cfg)
-        if bp <= 0 or bc <= 0:
+        c = self._glds_cfg(a.cfg)
+        if c is None:
             return 0
         M = a.N * a.P * a.Q
-        return ((M + bp - 1) // bp) * ((a.K + bc - 1) // bc) * ks * bp * bc
+        return ((M + c.bp - 1) // c.bp) * ((a.K + c.bc - 1) // c.bc) * ks * c.bp * c.bc
+
+    @staticmethod
+    def _glds_cfg(cfg):
+        """The library's DrnConvCfgInfo of an LDS-DMA tile configuration id; None for any other id."""
+        c = _lib.conv_cfg_info(cfg)
+        return c if c is not None and c.kind == 0 else None
 
     def _set_ksplit(self, a, ks: int):
         """ks > 1: split-K factor; ks < 0: stream-K over -ks workgroups (DrnConvFwdArgs.sk_blocks;
@@ -394,7 +405,7 @@ class HipBackend(_Common):
         if not (0 <= cfg < self.L.drn_conv_glds_num_cfgs()) or not self.L.drn_conv_glds_ok(ctypes.byref(a)):
             return False
         if ks > 1:
-            return self.L.drn_conv_glds_cfg_bk(cfg) > 0 and a.out_stride == 0
+            return bool(self._glds_cfg(cfg).ks) and a.out_stride == 0
         if ks < 0:
             return a.out_stride == 0 and self.L.drn_conv_sk_slots_cfg(ctypes.byref(a), cfg, -ks) > 0
         return True
@@ -476,10 +487,9 @@ class HipBackend(_Common):
         pairs = []
         for cfg in cands:
             pairs.append((cfg, 1))
-            bp = self.L.drn_conv_glds_cfg_bp(cfg) if 0 <= cfg < 1000 else 0
-            bc = self.L.drn_conv_glds_cfg_bc(cfg) if 0 <= cfg < 1000 else 0
-            if bp > 0 and bc > 0 and a.out_stride == 0:
-                tiles = ((M + bp - 1) // bp) * ((a.K + bc - 1) // bc)
+            c = self._glds_cfg(cfg)
+            if c is not None and a.out_stride == 0:
+                tiles = ((M + c.bp - 1) // c.bp) * ((a.K + c.bc - 1) // c.bc)
                 if tiles < 512:
                     pairs += [(cfg, k) for k in self.KS_FACTORS if k > 1]
                 if tiles < 1024:  # stream-K: every CU gets the same share of tile k-stages
@@ -607,7 +617,7 @@ class HipBackend(_Common):
         real launch that follows)."""
         iters = iters or self.tune_iters
         st = self.stream()
-        cands = tuple(int(c) for c in os.environ.get("DRN_WGRAD_CANDS", "0,2,3,4,5,6,7,8,9,10").split(","))
+        cands = tuple(int(c) for c in os.environ.get("DRN_WGRAD_CANDS", WGRAD_PIPELINES).split(","))
         seen = set()
         modes = (False, True) if self.wgrad_atomic_ok else (False,)
 
@@ -655,7 +665,7 @@ class HipBackend(_Common):
             raise RuntimeError(f"untuned weight gradient {key} while recording a step (tune it eagerly first)")
         if key not in self.wgrad_ns and self.autotune and not torch.cuda.is_current_stream_capturing():
             hit = self.tune_db().get_wgrad(key)
-            cands = [int(c) for c in os.environ.get("DRN_WGRAD_CANDS", "0,2,3,4,5,6,7,8,9,10").split(",")]
+            cands = [int(c) for c in os.environ.get("DRN_WGRAD_CANDS", WGRAD_PIPELINES).split(",")]
             if hit is not None and (not hit[2] or self.wgrad_atomic_ok) and hit[1] in cands:
                 self.db_hits += 1
                 self.wgrad_ns[key] = hit

@@ -174,21 +174,17 @@ def build(force: bool = False, verbose: bool = True, extra: list[str] | None = N
     return LIB_PATH
 
 
-def build_variant(out_dir: str, extra: list[str], src_root: Optional[str] = None) -> Path:
+def build_variant(out_dir: str, extra: list[str]) -> Path:
     """A diagnostics / A-B variant of the kernel library (e.g. extra=["-DDRN_CONV_TRACE"]) built
     into out_dir/libdrn_kernels.so with its own objects; load it with DRN_KERNEL_LIB=<path>
-    (the source-stamp check is skipped for an explicit library). src_root: a directory holding
-    kernels/ and include/ to build instead of csrc/ (patched copies for experiments, e.g.
-    scripts/conv_bound_iso.py)."""
+    (the source-stamp check is skipped for an explicit library)."""
     out = Path(out_dir).resolve()
     obj_dir = REPO / "build" / ("variant_" + out.parent.name + "_" + out.name)  # objects stay out of the tree
     out.mkdir(parents=True, exist_ok=True)
     obj_dir.mkdir(parents=True, exist_ok=True)
-    kdir = Path(src_root) / "kernels" if src_root else KERNELS
-    inc = Path(src_root) / "include" if src_root else INCLUDE
-    srcs = sorted(kdir.glob("*.hip"))
+    srcs = sources()
     with cf.ThreadPoolExecutor(max_workers=min(len(srcs), 8)) as ex:
-        objs = list(ex.map(lambda s: _compile(s, list(extra), obj_dir, inc), srcs))
+        objs = list(ex.map(lambda s: _compile(s, list(extra), obj_dir), srcs))
     objs.append(_stamp_object())
     lib = out / "libdrn_kernels.so"
     cmd = [hipcc(), f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", str(lib)] + [str(o) for o in objs]

@@ -1,9 +1,8 @@
 #!/usr/bin/env python3
 """What bounds the LDS-DMA convolution main loops? (isolate before tuning.)
 
-The same kernels are built in four variants from a patched copy of the sources
-(scripts/conv_bound_iso.patch; the shipped sources, and so the kernel database key, stay
-unchanged), and a fixed set of ResNet-50 bs128 launches -- the in-step configurations of the
+The same kernels are built in four variants from the shipped sources (the DRN_ISO_* #ifdef hooks
+in the main loops of conv_fwd.hip / conv_wgrad.hip, compiled out by default), and a fixed set of ResNet-50 bs128 launches -- the in-step configurations of the
 round-5 per-dispatch profile (profiles/r5_rn50_pmc_dispatch.txt) -- is timed under each:
 
   base    the real kernel
@@ -20,7 +19,6 @@ import argparse
 import ctypes
 import json
 import os
-import shutil
 import subprocess
 import sys
 
@@ -69,18 +67,11 @@ def add_sweep():
 
 
 def build(only=None):
-    src = os.path.join(REPO, "build", "iso_src")
-    shutil.rmtree(src, ignore_errors=True)
-    os.makedirs(src)
-    for d in ("kernels", "include"):
-        shutil.copytree(os.path.join(REPO, "csrc", d), os.path.join(src, "csrc", d))
-    subprocess.run(["patch", "-p0", "-s", "-i", os.path.join(REPO, "scripts", "conv_bound_iso.patch")], cwd=src,
-                   check=True)
     from distributed_resnet_tensorflow_amd.ops.build import build_variant
     for name, flags in VARIANTS.items():
         if only and name not in only:
             continue
-        lib = build_variant(os.path.join(OUT_ROOT, name), flags, src_root=os.path.join(src, "csrc"))
+        lib = build_variant(os.path.join(OUT_ROOT, name), flags)
         print(f"[iso] built {name}: {lib}", flush=True)
 
 

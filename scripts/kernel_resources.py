@@ -12,21 +12,31 @@ from pathlib import Path
 ROOT = Path(__file__).resolve().parents[1]
 
 
-def resources(src: str, include: str = str(ROOT / "csrc" / "include")) -> dict:
-    cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-I", include, "-c", src,
-           "-o", "/dev/null", "-Rpass-analysis=kernel-resource-usage"]
-    res = subprocess.run(cmd, capture_output=True, text=True)
+REMARKS = "-Rpass-analysis=kernel-resource-usage"
+
+
+def parse_remarks(lines) -> dict:
+    """{mangled kernel name: {VGPRs, AGPRs, Occupancy, VGPRs_spill, ScratchSize, LDS}} from the
+    compiler's kernel-resource-usage remarks (an iterable of stderr lines)."""
     out, cur = {}, None
-    for line in res.stderr.splitlines():
+    for line in lines:
         m = re.search(r"Function Name: (\S+)", line)
         if m:
             cur = m.group(1)
             out[cur] = {}
             continue
-        m = re.search(r"(VGPRs|AGPRs|Occupancy \[waves/SIMD\]|VGPRs Spill|LDS Size \[bytes/block\]): (\d+)", line)
+        m = re.search(r"(VGPRs|AGPRs|Occupancy \[waves/SIMD\]|VGPRs Spill|ScratchSize \[bytes/lane\]|"
+                      r"LDS Size \[bytes/block\]): (\d+)", line)
         if m and cur:
             out[cur][m.group(1).split(" ")[0] + ("_spill" if "Spill" in m.group(1) else "")] = int(m.group(2))
     return out
+
+
+def resources(src: str, include: str = str(ROOT / "csrc" / "include")) -> dict:
+    cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-I", include, "-c", src,
+           "-o", "/dev/null", REMARKS]
+    res = subprocess.run(cmd, capture_output=True, text=True)
+    return parse_remarks(res.stderr.splitlines())
 
 
 def main():

@@ -4,11 +4,12 @@ kernels untouched.
 
 The database section is keyed by the hash of the tuning sources (ops/build.py tune_hash): any edit
 of conv_fwd.hip / conv_wgrad.hip / stem.hip or a shared header retires every shipped choice, and a
-fresh rebuild re-times all of them (with its own run-to-run noise). When an edit only ADDS a kernel
-(e.g. a new weight-gradient pipeline) the existing choices stay valid: this script re-keys the
-newest section to the current hash and drops the entries the new code can improve, so those -- and
-only those -- are tuned again (by the next run, or thoroughly by scripts/make_tune_db.py pointed at
-the result with DRN_TUNE_DB_SYSTEM=off).
+fresh rebuild re-times all of them (with its own run-to-run noise). After an edit that leaves every
+tuned kernel's machine code unchanged, as shown by scripts/kernel_isa_diff.py (a refactor, or an
+edit that only adds kernels, e.g. a new weight-gradient pipeline), the existing choices stay valid:
+this script re-keys the newest section to the current hash and drops the entries the new code can
+improve, so those -- and only those -- are tuned again (by the next run, or thoroughly by
+scripts/make_tune_db.py pointed at the result with DRN_TUNE_DB_SYSTEM=off).
 
     python scripts/tune_db_rekey.py [--drop-wgrad KEYPREFIX ...] [--drop-conv KEYPREFIX ...] [--out PATH]
 """

@@ -89,11 +89,33 @@ GLDS_CASES = [
 ]
 
 
-N_GLDS = 38                              # one-tile LDS-DMA configurations (DRN_GLDS_NCFG)
+N_GLDS = 38                              # one-tile LDS-DMA configurations (kGldsCfg, conv_fwd.hip)
 BK32 = set(range(17, 23)) | {25, 27, 28, 29, 30, 33, 36, 37}  # 32-deep stages: C % 32 == 0 suffices
 BIG = set(range(25, 31)) | {33, 34}      # 8-wave big tiles: no row-staged narrow inputs
 IL = set(range(31, 38))                  # interleaved-DMA twins: no row-staged narrow inputs
 KS = [0, 13, 25, 31, 32, 33]             # split-K capable
+
+
+def test_conv_cfg_table_matches_literals(hip):
+    """The literal id sets above (kept literal so test ids do not depend on a loaded library)
+    against the library's own configuration table (drn_conv_cfg_info); no kernel launch.
+    BIG is not all of nw == 8: the 8-wave 64-deep one-slice tiles 8-11 take row-staged narrow
+    inputs and are tested with them; BIG is the 8-wave configurations that refuse them."""
+    from distributed_resnet_tensorflow_amd.ops import _lib
+    assert hip.L.drn_conv_glds_num_cfgs() == N_GLDS
+    table = [_lib.conv_cfg_info(i) for i in range(N_GLDS)]
+    assert all(c is not None and c.kind == 0 for c in table)
+    assert _lib.conv_cfg_info(N_GLDS) is None and _lib.conv_cfg_info(-1) is None and _lib.conv_cfg_info(100) is None
+    assert {i for i, c in enumerate(table) if c.bk == 32} == BK32
+    assert {i for i, c in enumerate(table) if c.nw == 8} == BIG | {8, 9, 10, 11}
+    assert {i for i, c in enumerate(table) if c.nw == 8 and (c.bk == 32 or c.nh > 1 or c.il)} == BIG
+    assert {i for i, c in enumerate(table) if c.il} == IL
+    assert {i for i, c in enumerate(table) if c.ks} == set(KS)
+    assert all(c.bk in (32, 64) and c.ns >= 2 and c.nw in (4, 8) and c.bp % 16 == 0 and c.bc % 16 == 0 for c in table)
+    nk0 = hip.L.drn_conv_nk_cfg0()
+    nk = [_lib.conv_cfg_info(nk0 + i) for i in range(hip.L.drn_conv_nk_num_cfgs())]
+    assert [(c.kind, c.bp, c.bc) for c in nk] == [(1, 128, 16), (1, 256, 16), (1, 64, 32), (1, 128, 32), (1, 256, 32)]
+    assert _lib.conv_cfg_info(nk0 + len(nk)) is None
 
 
 @pytest.mark.parametrize("case", GLDS_CASES)
