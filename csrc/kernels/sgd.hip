@@ -21,6 +21,8 @@ __device__ __forceinline__ float4 grad4(const bf16_t* g, int64_t i) {
   return make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u), __uint_as_float(u.y << 16),
                      __uint_as_float(u.y & 0xffff0000u));
 }
+__device__ __forceinline__ float grad1(const float* g, int64_t i) { return g[i]; }
+__device__ __forceinline__ float grad1(const bf16_t* g, int64_t i) { return bf2f(g[i]); }
 
 template <typename G>
 __global__ __launch_bounds__(256) void sgd_momentum_kernel(float* __restrict__ w, float* __restrict__ m,
@@ -66,6 +68,181 @@ __global__ __launch_bounds__(256) void sgd_momentum_kernel(float* __restrict__ w
     const float4 g0 = grad4(g, i);
     upd(w0, m0, g0);
     store(i, w0, m0);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// LARS (layer-wise adaptive rate scaling, You/Gitman/Ginsburg 2017; the apex "LARC" form):
+//   wn = ||w_l||  gn = ||gs * g_l||   trust_l = eta * wn / (gn + wd * wn + eps)  (1 if wn or gn is 0,
+//   1 for non-adapting slots)         g' = trust_l * (gs * g + wd * w) ; then the momentum update above.
+// Two launches over a device-resident slot table (one entry per variable of the flat buffer):
+// a norms pass and an update pass, both laid over (slot, chunk) pairs found through the table's
+// chunk prefix sums (as weight_tflip_kernel finds its descriptor). Every partial sum has a fixed
+// home in the workspace and is combined in a fixed order -- no floating-point atomics -- so every
+// data-parallel rank derives bit-identical trust ratios from the same reduced gradient.
+struct LarsSlot {
+  int64_t offset;          // first element in the flat buffers (a multiple of 4)
+  int32_t numel, padded;   // elements updated / slot length up to the next slot (padding is left alone)
+  int32_t adapt, pad_;     // 0: trust = 1 (BatchNorm gamma / beta, biases)
+  int64_t begin;           // prefix sum of chunk counts; entry [n] of an n-slot table holds the total
+};
+
+constexpr int LARS_CHUNK4 = 2048;  // float4 groups per chunk: 8 per thread (8192 elements)
+constexpr int LARS_GRID = 2048;    // workgroups (8 per CU); each strides over the range's chunks
+
+// slot owning chunk b (uniform scalar binary search over [s0, s0 + n))
+__device__ __forceinline__ int lars_find(const LarsSlot* __restrict__ table, int s0, int n, int64_t b) {
+  int lo = s0, hi = s0 + n - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (table[mid].begin <= b) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
+// sum of (a, b) over the workgroup, identical in every thread: wave64 butterfly, then the four wave
+// sums through LDS added in wave order (red: 8 floats; safe to call back to back)
+__device__ __forceinline__ void lars_block_sum(float& a, float& b, float* red) {
+  a = wave_sum(a);
+  b = wave_sum(b);
+  const int wave = threadIdx.x >> 6;
+  __syncthreads();  // the previous call's readers are done with red
+  if ((threadIdx.x & 63) == 0) { red[wave] = a; red[4 + wave] = b; }
+  __syncthreads();
+  a = ((red[0] + red[1]) + red[2]) + red[3];
+  b = ((red[4] + red[5]) + red[6]) + red[7];
+}
+
+template <typename G>
+__global__ __launch_bounds__(256) void lars_norms_kernel(const float* __restrict__ w, const G* __restrict__ g,
+                                                         const LarsSlot* __restrict__ table, int first_slot,
+                                                         int nslots, float* __restrict__ partials, float grad_scale,
+                                                         const int* __restrict__ skip) {
+  __shared__ float red[8];
+  if (skip != nullptr && *skip != 0) return;
+  const int64_t b0 = table[first_slot].begin, b1 = table[first_slot + nslots].begin;
+  for (int64_t b = b0 + blockIdx.x; b < b1; b += gridDim.x) {
+    const LarsSlot d = table[lars_find(table, first_slot, nslots, b)];
+    if (!d.adapt) continue;
+    const int c = (int)(b - d.begin);
+    const int64_t base4 = d.offset / 4;
+    const int full4 = d.numel >> 2;  // whole float4 groups; the last elements of the slot go one by one
+    const int i0 = c * LARS_CHUNK4;
+    const int i1 = min(i0 + LARS_CHUNK4, full4);
+    float sw = 0.f, sg = 0.f;
+    for (int i = i0 + threadIdx.x; i < i1; i += 256) {
+      const float4 wv = reinterpret_cast<const float4*>(w)[base4 + i];
+      float4 gv = grad4(g, base4 + i);
+      gv.x *= grad_scale; gv.y *= grad_scale; gv.z *= grad_scale; gv.w *= grad_scale;
+      sw += wv.x * wv.x; sw += wv.y * wv.y; sw += wv.z * wv.z; sw += wv.w * wv.w;
+      sg += gv.x * gv.x; sg += gv.y * gv.y; sg += gv.z * gv.z; sg += gv.w * gv.w;
+    }
+    // numel % 4 trailing elements belong to the slot's last chunk
+    if (threadIdx.x == 0 && (full4 << 2) < d.numel && i0 + LARS_CHUNK4 > full4 && i0 <= full4) {
+      for (int e = full4 << 2; e < d.numel; ++e) {
+        const float wv = w[d.offset + e];
+        const float gv = grad1(g, d.offset + e) * grad_scale;
+        sw += wv * wv;
+        sg += gv * gv;
+      }
+    }
+    lars_block_sum(sw, sg, red);
+    if (threadIdx.x == 0) {
+      partials[2 * b] = sw;
+      partials[2 * b + 1] = sg;
+    }
+  }
+}
+
+// The slot's partial sums are re-added by every workgroup of the slot (fixed order: thread t takes
+// partials t, t + 256, ..., then lars_block_sum) instead of by a finalize kernel between the two
+// passes: at most a few hundred L2-resident floats per workgroup, against a third dependent launch
+// (~6 us) in front of every update -- three of them in a deferred-tail step.
+template <typename G>
+__global__ __launch_bounds__(256) void lars_update_kernel(float* __restrict__ w, float* __restrict__ m,
+                                                          const G* __restrict__ g, bf16_t* __restrict__ wb,
+                                                          const LarsSlot* __restrict__ table, int first_slot,
+                                                          int nslots, const float* __restrict__ partials,
+                                                          float* __restrict__ trust_out,
+                                                          const float* __restrict__ lr_ptr, float mu, float wd,
+                                                          float grad_scale, float eta, float eps,
+                                                          const int* __restrict__ skip) {
+  __shared__ float red[8];
+  if (skip != nullptr && *skip != 0) return;
+  const float lr = *lr_ptr;
+  const int64_t b0 = table[first_slot].begin, b1 = table[first_slot + nslots].begin;
+  for (int64_t b = b0 + blockIdx.x; b < b1; b += gridDim.x) {
+    const int slot = lars_find(table, first_slot, nslots, b);
+    const LarsSlot d = table[slot];
+    const int c = (int)(b - d.begin);
+    float trust = 1.f;
+    if (d.adapt) {
+      const int nchunk = (int)(table[slot + 1].begin - d.begin);
+      float sw = 0.f, sg = 0.f;
+      for (int j = threadIdx.x; j < nchunk; j += 256) {
+        sw += partials[2 * (d.begin + j)];
+        sg += partials[2 * (d.begin + j) + 1];
+      }
+      lars_block_sum(sw, sg, red);
+      if (sw > 0.f && sg > 0.f) {
+        const float wn = sqrtf(sw), gn = sqrtf(sg);
+        trust = eta * wn / (gn + wd * wn + eps);
+      }
+    }
+    if (c == 0 && threadIdx.x == 0) trust_out[slot] = trust;
+    // with trust == 1 bit for bit the update of sgd_momentum_kernel
+    auto upd1 = [&](float& wv, float& mv, float gv) {
+      const float gg = trust * (gv * grad_scale + wd * wv);
+      mv = __builtin_fmaf(mu, mv, gg);
+      wv -= lr * mv;
+    };
+    auto upd = [&](float4& wv, float4& mv, const float4& gv) {
+      upd1(wv.x, mv.x, gv.x); upd1(wv.y, mv.y, gv.y); upd1(wv.z, mv.z, gv.z); upd1(wv.w, mv.w, gv.w);
+    };
+    auto store = [&](int64_t i, const float4& wv, const float4& mv) {
+      reinterpret_cast<float4*>(w)[i] = wv;
+      reinterpret_cast<float4*>(m)[i] = mv;
+      if (wb) {
+        uint2 o;
+        o.x = pack2bf(wv.x, wv.y);
+        o.y = pack2bf(wv.z, wv.w);
+        reinterpret_cast<uint2*>(wb)[i] = o;
+      }
+    };
+    const int64_t base4 = d.offset / 4;
+    const int full4 = d.numel >> 2;
+    const int i0 = c * LARS_CHUNK4;
+    const int i1 = min(i0 + LARS_CHUNK4, full4);
+    // two float4 groups in flight per thread, as in sgd_momentum_kernel
+    int i = i0 + threadIdx.x;
+    for (; i + 256 < i1; i += 512) {
+      const int64_t p = base4 + i, q = p + 256;
+      float4 w0 = reinterpret_cast<float4*>(w)[p], w1 = reinterpret_cast<float4*>(w)[q];
+      float4 m0 = reinterpret_cast<float4*>(m)[p], m1 = reinterpret_cast<float4*>(m)[q];
+      const float4 g0 = grad4(g, p), g1 = grad4(g, q);
+      upd(w0, m0, g0);
+      upd(w1, m1, g1);
+      store(p, w0, m0);
+      store(q, w1, m1);
+    }
+    if (i < i1) {
+      const int64_t p = base4 + i;
+      float4 w0 = reinterpret_cast<float4*>(w)[p];
+      float4 m0 = reinterpret_cast<float4*>(m)[p];
+      const float4 g0 = grad4(g, p);
+      upd(w0, m0, g0);
+      store(p, w0, m0);
+    }
+    if (threadIdx.x == 0 && (full4 << 2) < d.numel && i0 + LARS_CHUNK4 > full4 && i0 <= full4) {
+      for (int e = full4 << 2; e < d.numel; ++e) {
+        const int64_t p = d.offset + e;
+        float wv = w[p], mv = m[p];
+        upd1(wv, mv, grad1(g, p));
+        w[p] = wv;
+        m[p] = mv;
+        if (wb) wb[p] = f2bf(wv);
+      }
+    }
   }
 }
 
@@ -174,6 +351,34 @@ DRN_API int drn_sgd_momentum(float* w, float* m, const void* g, int g_bf16, void
                        (const float*)g, (bf16_t*)w_bf16, n / 4, lr_ptr, momentum, wd, grad_scale, skip);
   return (int)hipGetLastError();
 }
+
+// LARS + momentum over table slots [first_slot, first_slot + nslots) of the flat buffers (w, m, g,
+// w_bf16 are the buffers' bases: the table holds absolute element offsets). table: LarsSlot entries
+// with one closing entry (its begin = total chunks); partials: 2 floats per chunk of the whole
+// table; trust: one float per slot. skip as in drn_sgd_momentum (trust is left alone too).
+DRN_API int drn_lars_momentum(float* w, float* m, const void* g, int g_bf16, void* w_bf16, const void* table,
+                              int first_slot, int nslots, float* partials, float* trust, const float* lr_ptr,
+                              float momentum, float wd, float grad_scale, float eta, float eps, const int* skip,
+                              hipStream_t s) {
+  if (first_slot < 0 || nslots < 1) return (int)hipErrorInvalidValue;
+  const drn::LarsSlot* t = (const drn::LarsSlot*)table;
+  const dim3 grid(drn::LARS_GRID), block(256);
+  if (g_bf16) {
+    drn::launch(drn::lars_norms_kernel<bf16_t>, grid, block, 0, s, (const float*)w, (const bf16_t*)g, t, first_slot,
+                nslots, partials, grad_scale, skip);
+    drn::launch(drn::lars_update_kernel<bf16_t>, grid, block, 0, s, w, m, (const bf16_t*)g, (bf16_t*)w_bf16, t,
+                first_slot, nslots, (const float*)partials, trust, lr_ptr, momentum, wd, grad_scale, eta, eps, skip);
+  } else {
+    drn::launch(drn::lars_norms_kernel<float>, grid, block, 0, s, (const float*)w, (const float*)g, t, first_slot,
+                nslots, partials, grad_scale, skip);
+    drn::launch(drn::lars_update_kernel<float>, grid, block, 0, s, w, m, (const float*)g, (bf16_t*)w_bf16, t,
+                first_slot, nslots, (const float*)partials, trust, lr_ptr, momentum, wd, grad_scale, eta, eps, skip);
+  }
+  return (int)hipGetLastError();
+}
+
+DRN_API int drn_lars_slot_size() { return (int)sizeof(drn::LarsSlot); }
+DRN_API int drn_lars_chunk() { return drn::LARS_CHUNK4 * 4; }
 
 DRN_API int drn_cast_bf16(const float* x, void* y, int64_t n, hipStream_t s) {
   if (n % 4) return (int)hipErrorInvalidValue;

@@ -134,6 +134,7 @@ class FlagValues:
                     raise FlagsError(f"Flag --{name}: {e}") from e
             f.present = True
         object.__setattr__(self, "_parsed", True)
+        validate(self)
         return rest
 
     def reset(self):
@@ -145,6 +146,19 @@ class FlagValues:
         for f in sorted(self._flags.values(), key=lambda x: x.name):
             lines.append(f"  --{f.name}: {f.help} (default: {f.default!r})")
         return "\n".join(lines)
+
+
+def validate(fv: "FlagValues") -> None:
+    """Cross-flag checks at parse time (flag sets that do not define a flag skip its checks)."""
+    if "optimizer" not in fv:
+        return
+    if fv.optimizer not in ("momentum", "lars"):
+        raise FlagsError(f"--optimizer must be momentum or lars, got {fv.optimizer!r}")
+    if fv.lr_policy not in ("reference", "poly"):
+        raise FlagsError(f"--lr_policy must be reference or poly, got {fv.lr_policy!r}")
+    if fv.optimizer == "lars" and fv.optimizer_sharding:
+        raise FlagsError("--optimizer=lars cannot be combined with --optimizer_sharding: a sharded update cuts "
+                         "tensors across ranks and LARS needs each tensor's whole norm")
 
 
 FLAGS = FlagValues()
@@ -229,6 +243,16 @@ def define_reference_flags(flag_values: FlagValues = FLAGS, **defaults) -> FlagV
     B("optimizer_sharding", False, "ZeRO-1-style sharded optimizer (the parameter-server sharding analog, "
       "SURVEY P3): reduce-scatter the gradient buckets, update 1/N of the weights and momentum per rank, "
       "all-gather the bf16 compute weights.", fv)
+    S("optimizer", "momentum", "momentum (the reference's MomentumOptimizer) or lars (layer-wise adaptive rate "
+      "scaling on conv / dense kernels, for large global batches; fused HIP kernels).", fv)
+    Fl("lars_eta", 0.001, "LARS trust coefficient: trust = eta * |w| / (|g| + wd * |w| + eps).", fv)
+    Fl("lars_eps", 1e-9, "LARS epsilon in the trust ratio's denominator.", fv)
+    S("lr_policy", "reference", "reference (the reference scripts' step tables) or poly (linear warm-up from 0 "
+      "to --peak_lr over --warmup_steps, then polynomial decay to --end_lr at --train_steps).", fv)
+    Fl("peak_lr", 0.1, "--lr_policy=poly: learning rate at the end of the warm-up.", fv)
+    I("warmup_steps", 0, "--lr_policy=poly: linear warm-up steps.", fv)
+    Fl("poly_power", 2.0, "--lr_policy=poly: power of the polynomial decay.", fv)
+    Fl("end_lr", 0.0, "--lr_policy=poly: learning rate at --train_steps.", fv)
     I("collective_timeout_secs", 600, "Process-group timeout and collective-watchdog limit: a rank whose "
       "gradient exchange stalls this long exits (the launcher restarts the job from its checkpoint).", fv)
     I("fault_inject_step", -1, "Kill this process at the given global step (fault-injection tests).", fv)

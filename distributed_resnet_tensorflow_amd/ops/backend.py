@@ -78,6 +78,50 @@ def tflip_table(descs):
     return torch.from_numpy(arr.view(np.uint8).copy()), len(descs), begin
 
 
+LARS_SLOT = np.dtype([("offset", "<i8"), ("numel", "<i4"), ("padded", "<i4"), ("adapt", "<i4"), ("pad_", "<i4"),
+                      ("begin", "<i8")])  # mirror of sgd.hip `struct LarsSlot`
+LARS_CHUNK = 8192                         # elements per work chunk (sgd.hip LARS_CHUNK4 * 4)
+LARS_EXCLUDED = ("gamma", "beta", "dense_b")  # slot kinds whose trust ratio is fixed at 1
+
+
+class LarsTable:
+    """The slot table of lars_momentum. slots: (offset, numel, padded, adapt) per variable in buffer
+    order; offsets are multiples of 4 elements and slots do not overlap. `arr` (numpy, LARS_SLOT)
+    has one closing entry whose `begin` is the total chunk count; `dev` is its byte image on
+    `device` (what the HIP kernels read)."""
+
+    def __init__(self, slots, device="cpu"):
+        self.n = len(slots)
+        arr = np.zeros(self.n + 1, dtype=LARS_SLOT)
+        begin = end = 0
+        for i, (off, numel, padded, adapt) in enumerate(slots):
+            if off % 4 or off < end or numel < 1 or padded < numel:
+                raise ValueError(f"bad LARS slot {i}: offset {off}, numel {numel}, padded {padded}")
+            arr[i] = (off, numel, padded, int(bool(adapt)), 0, begin)
+            begin += -(-numel // LARS_CHUNK)
+            end = off + padded
+        arr[self.n]["offset"], arr[self.n]["begin"] = end, begin
+        self.arr, self.chunks = arr, begin
+        self.dev = torch.from_numpy(arr.view(np.uint8).copy()).to(device)
+
+    def slot_range(self, lo: int, hi: int):
+        """(first_slot, nslots) of the flat element range [lo, hi); ValueError if it cuts a slot."""
+        off, end = self.arr["offset"][:self.n], self.arr["offset"][:self.n] + self.arr["padded"][:self.n]
+        first, last = int(np.searchsorted(off, lo, "left")), int(np.searchsorted(end, hi, "right"))
+        if first > 0 and end[first - 1] > lo or last < self.n and off[last] < hi:
+            raise ValueError(f"range [{lo}, {hi}) cuts a parameter slot: LARS needs whole tensors")
+        if last <= first:
+            raise ValueError(f"range [{lo}, {hi}) holds no parameter slot")
+        return first, last - first
+
+
+def lars_table(store, device=None) -> LarsTable:
+    """The LarsTable of a runtime.params.ParamStore (built once per store)."""
+    from ..runtime.params import _round
+    return LarsTable([(s.offset, s.numel, _round(s.numel), s.kind not in LARS_EXCLUDED) for s in store.slots],
+                     store.device if device is None else device)
+
+
 def _aligned16(*ts):
     """The fused BN kernels read per-channel vectors with 16-byte loads."""
     for t in ts:
@@ -876,6 +920,27 @@ class HipBackend(_Common):
                                            _ptr(wb), w.numel(), lr_t.data_ptr(), float(momentum), float(wd),
                                            float(grad_scale), _ptr(skip), self.stream()), "drn_sgd_momentum")
 
+    def lars_momentum(self, w, m, g, wb, table: LarsTable, first_slot, nslots, partials, trust, lr_t, momentum, wd,
+                      grad_scale, eta, eps, skip=None):
+        """Fused LARS + momentum (sgd.hip) on slots [first_slot, first_slot + nslots) of `table`.
+        w, m, g, wb are the whole flat buffers the table's offsets index; partials (2 fp32 per chunk
+        of the table) and trust (1 fp32 per slot) are the caller's preallocated workspaces; trust
+        receives every updated slot's ratio. skip as in sgd_momentum (then trust is left alone too)."""
+        assert g.dtype in (torch.float32, torch.bfloat16) and g.numel() == w.numel() == m.numel()
+        assert 0 <= first_slot and nslots >= 1 and first_slot + nslots <= table.n
+        assert int(table.arr["offset"][table.n]) <= w.numel() and table.dev.device == w.device
+        assert partials.numel() >= 2 * table.chunks and trust.numel() >= table.n
+        assert partials.dtype == trust.dtype == torch.float32 and (wb is None or wb.numel() == w.numel())
+        if not getattr(self, "_lars_checked", False):
+            if self.L.drn_lars_slot_size() != LARS_SLOT.itemsize or self.L.drn_lars_chunk() != LARS_CHUNK:
+                raise _lib.KernelLibraryError("LarsSlot layout mismatch between Python and the kernel library")
+            self._lars_checked = True
+        _lib.check(self.L.drn_lars_momentum(w.data_ptr(), m.data_ptr(), g.data_ptr(), int(g.dtype == torch.bfloat16),
+                                            _ptr(wb), table.dev.data_ptr(), int(first_slot), int(nslots),
+                                            partials.data_ptr(), trust.data_ptr(), lr_t.data_ptr(), float(momentum),
+                                            float(wd), float(grad_scale), float(eta), float(eps), _ptr(skip),
+                                            self.stream()), "drn_lars_momentum")
+
     def cast_bf16(self, x, y):
         _lib.check(self.L.drn_cast_bf16(x.data_ptr(), y.data_ptr(), x.numel(), self.stream()), "drn_cast_bf16")
 
@@ -1210,6 +1275,32 @@ class RefBackend(_Common):
         w.sub_(lr * m)
         if wb is not None and wb.data_ptr() != w.data_ptr():
             wb.copy_(w)
+
+    def lars_momentum(self, w, m, g, wb, table: LarsTable, first_slot, nslots, partials, trust, lr_t, momentum, wd,
+                      grad_scale, eta, eps, skip=None):
+        """HipBackend.lars_momentum's contract in torch, in the dtype of w (the oracle: fp64 under
+        RefBackend(dtype=torch.float64)). partials is not used."""
+        if skip is not None and int(skip.reshape(-1)[0]) != 0:
+            return
+        lr = float(lr_t.reshape(-1)[0])
+        for i in range(first_slot, first_slot + nslots):
+            d = table.arr[i]
+            sl = slice(int(d["offset"]), int(d["offset"]) + int(d["numel"]))
+            ws, ms = w[sl], m[sl]
+            gs = g[sl].to(w.dtype) * grad_scale
+            t = 1.0
+            if d["adapt"]:
+                wn, gn = float(torch.linalg.vector_norm(ws)), float(torch.linalg.vector_norm(gs))
+                if wn > 0 and gn > 0:
+                    t = eta * wn / (gn + wd * wn + eps)
+            gg = gs + wd * ws
+            if t != 1.0:
+                gg = gg * t
+            ms.mul_(momentum).add_(gg)
+            ws.sub_(lr * ms)
+            if wb is not None and wb.data_ptr() != w.data_ptr():
+                wb[sl].copy_(ws)
+            trust[i] = t
 
     def cast_bf16(self, x, y):
         y.copy_(x)

@@ -134,6 +134,8 @@ class DataParallelEngine:
                 self.buckets = self._make_buckets(int(self.P.total // 60) + 1)
             self.p2p = P2PAllReduce(self.P.grad, group, wire=self.wire)
         self.zero1 = bool(shard_optimizer) and self.world > 1 and mode == "sync"
+        if self.zero1 and getattr(executor, "optimizer", "momentum") == "lars":
+            raise ValueError("optimizer sharding cuts tensors across ranks; LARS needs each tensor's whole norm")
         if self.zero1 and self.wire != "fp32":
             raise ValueError("optimizer sharding reduce-scatters fp32 gradients (--allreduce_wire=fp32)")
         # RCCL bf16 wire: a bf16 shadow of the flat gradient; each bucket is cast into it by an

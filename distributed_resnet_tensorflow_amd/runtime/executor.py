@@ -103,8 +103,15 @@ class Executor:
     GRAD_BUF_MAX = 64     # rotating data-gradient buffers of ImageNet-sized steps (see _alloc)
     def __init__(self, spec: NetSpec, batch: int, backend, device, seed: int = 0,
                  weight_decay: float = 2e-4, momentum: float = 0.9, params: ParamStore | None = None,
-                 materialize_bn: Optional[bool] = None):
+                 materialize_bn: Optional[bool] = None, optimizer: str = "momentum", lars_eta: float = 0.001,
+                 lars_eps: float = 1e-9):
         self.spec, self.N, self.be = spec, batch, backend
+        # "momentum": the reference's MomentumOptimizer; "lars": the same update with each conv /
+        # dense kernel's gradient (weight decay included) scaled by its layer-wise trust ratio
+        # eta * ||w|| / (||g|| + wd * ||w|| + eps) (csrc/kernels/sgd.hip), for large global batches
+        if optimizer not in ("momentum", "lars"):
+            raise ValueError(f"optimizer must be 'momentum' or 'lars', got {optimizer!r}")
+        self.optimizer, self.lars_eta, self.lars_eps = optimizer, float(lars_eta), float(lars_eps)
         # fuse each BN's backward reduction into the epilogue of the data-gradient conv feeding it
         self.fuse_bn_bwd = True
         # (The BN backward applied on load by both 1x1 consumers instead of materialised -- the
@@ -507,6 +514,14 @@ class Executor:
                     n *= d
                 ph.wt = self.wt_flat[ph.wt_off:ph.wt_off + n].view(ph.wt_shape)
         self.lr_t = self._f32(1)
+        # LARS: the slot table, the norms workspace and the per-slot trust ratios, allocated once
+        # (a captured graph / recorded plan replays with these pointers)
+        self.lars_table = self.lars_partials = self.lars_trust = None
+        if self.optimizer == "lars":
+            from ..ops.backend import lars_table
+            self.lars_table = lars_table(self.P, self.device)
+            self.lars_partials = self._f32(2 * self.lars_table.chunks)
+            self.lars_trust = torch.ones(self.lars_table.n, dtype=torch.float32, device=self.device)
 
     def _all_ops(self):
         yield self.stem_op
@@ -935,10 +950,24 @@ class Executor:
             ev, self._stem_ev = self._stem_ev, None
             self._join(ev)
 
+    def _update(self, lo: int, hi: int, g: torch.Tensor, grad_scale: float, skip=None):
+        """The optimizer's update of the flat range [lo, hi): every update of apply_gradients goes
+        through here. LARS works on whole tensors: a range that cuts a slot raises ValueError."""
+        P = self.P
+        if self.optimizer == "lars":
+            first, n = self.lars_table.slot_range(lo, hi)
+            self.be.lars_momentum(P.master, P.momentum, g, P.wbf16, self.lars_table, first, n, self.lars_partials,
+                                  self.lars_trust, self.lr_t, self.mom, self.wd, grad_scale, self.lars_eta,
+                                  self.lars_eps, skip)
+            return
+        wb = P.wbf16[lo:hi] if P.wbf16 is not None else None
+        self.be.sgd_momentum(P.master[lo:hi], P.momentum[lo:hi], g[lo:hi], wb, self.lr_t, self.mom, self.wd,
+                             grad_scale, skip)
+
     def apply_gradients(self, grad_scale: float = 1.0, grad: Optional[torch.Tensor] = None,
                         skip: Optional[torch.Tensor] = None):
-        """Fused SGD-momentum + weight-layout refresh. skip: optional device int32 word; when it
-        is non-zero at run time no parameter or momentum changes (the P2P error word)."""
+        """Fused SGD-momentum (or LARS) + weight-layout refresh. skip: optional device int32 word;
+        when it is non-zero at run time no parameter or momentum changes (the P2P error word)."""
         P = self.P
         g = P.grad if grad is None else grad
         if self._tail_ev is not None and grad is None:
@@ -950,32 +979,27 @@ class Executor:
                 lo, pre = self._pre_lo, self._pre_ev
                 self._pre_ev = None
                 self.sched.wait(main, pre)
-                wb = P.wbf16[lo:] if P.wbf16 is not None else None
-                self.be.sgd_momentum(P.master[lo:], P.momentum[lo:], g[lo:], wb, self.lr_t, self.mom, self.wd,
-                                     grad_scale, skip)
+                self._update(lo, P.total, g, grad_scale, skip)
                 self.sched.wait(main, ev)
-                wb = P.wbf16[hi:lo] if P.wbf16 is not None else None
-                self.be.sgd_momentum(P.master[hi:lo], P.momentum[hi:lo], g[hi:lo], wb, self.lr_t, self.mom,
-                                     self.wd, grad_scale, skip)
+                self._update(hi, lo, g, grad_scale, skip)
             else:
                 self._pre_ev = None
                 self.sched.wait(main, ev)
-                wb = P.wbf16[hi:] if P.wbf16 is not None else None
-                self.be.sgd_momentum(P.master[hi:], P.momentum[hi:], g[hi:], wb, self.lr_t, self.mom, self.wd,
-                                     grad_scale, skip)
+                self._update(hi, P.total, g, grad_scale, skip)
             self.refresh_dgrad_weights(stem=False)  # (the stem's weights are not updated yet)
             self.join_grads()
-            wb = P.wbf16[:hi] if P.wbf16 is not None else None
-            self.be.sgd_momentum(P.master[:hi], P.momentum[:hi], g[:hi], wb, self.lr_t, self.mom, self.wd,
-                                 grad_scale, skip)
+            self._update(0, hi, g, grad_scale, skip)
             self._repack_stem()
             return
         self.join_grads()
-        self.be.sgd_momentum(P.master, P.momentum, g, P.wbf16, self.lr_t, self.mom, self.wd, grad_scale, skip)
+        self._update(0, P.total, g, grad_scale, skip)
         self.refresh_dgrad_weights()
 
     def sgd_range(self, lo: int, hi: int, grad_scale: float, grad: Optional[torch.Tensor] = None):
         """Fused SGD-momentum on the flat slice [lo, hi) only (sharded optimizer)."""
+        if self.optimizer == "lars":
+            raise RuntimeError("the sharded optimizer cuts tensors across ranks; LARS needs every tensor's whole "
+                               "norm (optimizer='lars' does not support optimizer sharding)")
         P = self.P
         g = P.grad if grad is None else grad
         wb = P.wbf16[lo:hi] if P.wbf16 is not None else None

@@ -88,8 +88,16 @@ class SummaryHook(Hook):
         if step % self.n:
             return
         m = metrics_fn()
-        self.w.add_scalars(step, {"cross_entropy": m["cross_entropy"], "cost": m["cost"],
-                                  "learning_rate": m["learning_rate"], "Precision": m["precision"]})
+        scalars = {"cross_entropy": m["cross_entropy"], "cost": m["cost"],
+                   "learning_rate": m["learning_rate"], "Precision": m["precision"]}
+        ex = getattr(sess, "ex", None)
+        if getattr(ex, "optimizer", "momentum") == "lars":
+            # the last update's trust ratios of the adapting (conv / dense kernel) slots
+            adapt = ex.lars_table.arr["adapt"][:ex.lars_table.n] != 0
+            t = ex.lars_trust.detach().cpu().numpy()[adapt].astype("float64")
+            scalars.update({"lars/trust_min": float(t.min()), "lars/trust_max": float(t.max()),
+                            "lars/trust_mean": float(t.mean())})
+        self.w.add_scalars(step, scalars)
 
     def end(self, sess):
         self.w.flush()

@@ -57,3 +57,31 @@ def for_dataset(dataset: str, step_scale: float = 1.0) -> LRSchedule:
     base = imagenet_lr if dataset == "imagenet" else cifar_lr
     fn = base if step_scale == 1.0 else (lambda step: base(int(step / step_scale)))
     return LRSchedule(fn, 0.4 if dataset == "imagenet" else 0.1)
+
+
+def poly_lr(step: int, peak_lr: float, warmup_steps: int, train_steps: int, power: float = 2.0,
+            end_lr: float = 0.0) -> float:
+    """Linear warm-up 0 -> peak_lr over warmup_steps, then polynomial decay
+    end_lr + (peak_lr - end_lr) * (1 - (step - warmup) / (train_steps - warmup)) ** power
+    (the usual companion of LARS; end_lr from train_steps on)."""
+    if step < warmup_steps:
+        return peak_lr * step / warmup_steps
+    span = max(1, train_steps - warmup_steps)
+    frac = min(1.0, (step - warmup_steps) / span)
+    return end_lr + (peak_lr - end_lr) * (1.0 - frac) ** power
+
+
+def poly(peak_lr: float, warmup_steps: int, train_steps: int, power: float = 2.0, end_lr: float = 0.0) -> LRSchedule:
+    """The poly policy under the LRSchedule protocol: the first step runs at poly_lr(0), every
+    later step at the value of the global step the previous step returned."""
+    if warmup_steps < 0 or train_steps <= warmup_steps:
+        raise ValueError(f"--lr_policy=poly needs 0 <= warmup_steps < train_steps, got {warmup_steps}, {train_steps}")
+    fn = lambda step: poly_lr(step, peak_lr, warmup_steps, train_steps, power, end_lr)  # noqa: E731
+    return LRSchedule(fn, fn(0))
+
+
+def from_flags(FLAGS) -> LRSchedule:
+    """--lr_policy=reference: for_dataset; poly: the warm-up / polynomial-decay schedule."""
+    if FLAGS.lr_policy == "poly":
+        return poly(FLAGS.peak_lr, FLAGS.warmup_steps, FLAGS.train_steps, FLAGS.poly_power, FLAGS.end_lr)
+    return for_dataset(FLAGS.dataset, FLAGS.lr_schedule_scale)

@@ -78,12 +78,14 @@ class TrainingSession:
                  max_to_keep: int = 5, seed: int = 0, use_graph: bool = True, sync_mode: str = "sync",
                  bucket_mb: float = 25.0, meta: Optional[dict] = None, allreduce: str = "rccl", wire: str = "fp32",
                  collective_timeout_s: float = 0.0, precision: str = "bf16", shard_optimizer: bool = False,
-                 step_trial: bool = True):
+                 step_trial: bool = True, optimizer: str = "momentum", lars_eta: float = 0.001,
+                 lars_eps: float = 1e-9):
         self.cluster = cluster
         self.spec = spec
         self.device = torch.device(cluster.device)
         self.be = make_backend(cluster.device, precision)
-        self.ex = Executor(spec, batch, self.be, self.device, seed=seed, weight_decay=weight_decay)
+        self.ex = Executor(spec, batch, self.be, self.device, seed=seed, weight_decay=weight_decay,
+                           optimizer=optimizer, lars_eta=lars_eta, lars_eps=lars_eps)
         self.lr = lr_schedule
         self.meta = meta or {}
         # DRN_FORCE_DP=1: the data-parallel engine on a single-rank process group (profiling the

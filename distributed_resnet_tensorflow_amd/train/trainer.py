@@ -52,7 +52,8 @@ def _meta(FLAGS, spec):
     return {"dataset": FLAGS.dataset, "resnet_size": FLAGS.resnet_size, "model": FLAGS.model,
             "width_multiplier": FLAGS.width_multiplier if FLAGS.model == "wide_resnet" else 1,
             "num_classes": spec.num_classes,
-            "spec_name": spec.name}
+            "spec_name": spec.name,
+            "optimizer": FLAGS.optimizer, "eta": FLAGS.lars_eta, "eps": FLAGS.lars_eps}
 
 
 def make_feeder(FLAGS, ex, cluster, is_training: bool, data_state=None, batch=None):
@@ -102,12 +103,13 @@ def train(FLAGS, cluster=None):
         if cluster.is_chief:
             log.info("--sync_replicas=False: 1-step-delayed all-reduce (async-PS analog, staleness 1; not "
                      "bit-equivalent to TF asynchronous parameter servers)")
-    sess = TrainingSession(spec, FLAGS.batch_size, cluster, weight_decay=wd, lr_schedule=lr_mod.for_dataset(FLAGS.dataset, FLAGS.lr_schedule_scale),
+    sess = TrainingSession(spec, FLAGS.batch_size, cluster, weight_decay=wd, lr_schedule=lr_mod.from_flags(FLAGS),
                            checkpoint_dir=FLAGS.log_root, max_to_keep=FLAGS.max_to_keep, seed=FLAGS.seed,
                            use_graph=FLAGS.hip_graph, sync_mode=sync_mode, bucket_mb=FLAGS.bucket_mb,
                            meta=_meta(FLAGS, spec), allreduce=FLAGS.allreduce, wire=FLAGS.allreduce_wire,
                            collective_timeout_s=FLAGS.collective_timeout_secs, precision=FLAGS.precision,
-                           shard_optimizer=FLAGS.optimizer_sharding)
+                           shard_optimizer=FLAGS.optimizer_sharding, optimizer=FLAGS.optimizer,
+                           lars_eta=FLAGS.lars_eta, lars_eps=FLAGS.lars_eps)
     feeder = make_feeder(FLAGS, sess.ex, cluster, True, sess.data_state)
     is_imagenet = FLAGS.dataset == "imagenet"
     hooks = [LoggingHook(FLAGS.log_every_n_steps, FLAGS.batch_size * cluster.world,
