@@ -1,5 +1,6 @@
 // head.hip — classifier head on gfx950: final BN-ReLU + global average pool, dense layer
-// (fp32 GEMMs), softmax cross-entropy with one-hot labels and the batch precision metric.
+// (fp32 GEMMs), softmax cross-entropy with one-hot labels and the batch precision metric, and its
+// label-smoothing / top-k variant (softmax_xent_ex_kernel).
 //
 // Reference: final batch_norm_relu + average_pooling2d(VALID, pool = H) + dense
 // (resnet_model_official.py:268-275 CIFAR, :336-343 ImageNet); softmax + mean
@@ -212,6 +213,107 @@ __global__ __launch_bounds__(256) void softmax_xent_kernel(const float* __restri
   }
 }
 
+// softmax_xent_kernel with a smoothed target and a top-k count (one block per sample, one launch):
+//   t_j     = (1 - eps) [j == y] + eps / K                     (K = ncls, eps = smoothing)
+//   loss    = log(se) - (1 - eps) (z_y - mx) - (eps / K) sum_j (z_j - mx)
+//   dlogits = (p_j - t_j) * grad_scale
+//   rank    = #{j : z_j > z_y} + #{j < y : z_j == z_y};  correct_k = rank < top_k (0 for a NaN z_y)
+// The max / argmax and the sum of exponentials are reduced exactly as in softmax_xent_kernel
+// (256 threads striding the row, wave reduction, waves in index order), so at eps = 0 probs,
+// dlogits and loss are the same bits and correct is the same rule; the two extra reductions (the rank
+// count, an integer, and sum_j (z_j - mx)) ride along the same two barriers. REG: rows of up to
+// 8 * 256 classes are read from memory once and kept in 8 registers per thread; longer rows are
+// re-read like softmax_xent_kernel does. A label outside [0, ncls) reads nothing: its loss is NaN,
+// its counts 0 and its gradient the plain p_j - eps / K.
+constexpr int XENT_REG_ROW = 8;  // row elements per thread held in registers
+
+template <bool REG>
+__global__ __launch_bounds__(256) void softmax_xent_ex_kernel(const float* __restrict__ logits,
+                                                              const int* __restrict__ labels, int ncls,
+                                                              float grad_scale, float smoothing, int top_k,
+                                                              float* __restrict__ dlogits, float* __restrict__ loss,
+                                                              float* __restrict__ probs, int* __restrict__ correct,
+                                                              int* __restrict__ correct_k) {
+  const int n = blockIdx.x;
+  const float* z = logits + (size_t)n * ncls;
+  __shared__ float sred[8], ssum[8];
+  __shared__ int sidx[8], scnt[8];
+  const int y = labels[n];
+  const bool yok = (unsigned)y < (unsigned)ncls;
+  const float zy = yok ? z[y] : __builtin_nanf("");
+  const int iters = REG ? XENT_REG_ROW : (ncls + 255) / 256;
+  float r[XENT_REG_ROW];
+  if (REG) {
+#pragma unroll
+    for (int i = 0; i < XENT_REG_ROW; ++i) {
+      const int j = threadIdx.x + 256 * i;
+      r[i] = j < ncls ? z[j] : -INFINITY;
+    }
+  }
+  // element i of this thread's stride (j = threadIdx.x + 256 * i < ncls)
+  auto at = [&](int i, int j) { return REG ? r[i] : z[j]; };
+  float mx = -INFINITY;
+  int amax = 0, cnt = 0;
+#pragma unroll
+  for (int i = 0; i < iters; ++i) {
+    const int j = threadIdx.x + 256 * i;
+    if (j < ncls) {
+      const float v = at(i, j);
+      if (v > mx) { mx = v; amax = j; }
+      cnt += (v > zy || (v == zy && j < y)) ? 1 : 0;
+    }
+  }
+  // block argmax (first index of the max) and the rank count
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(mx, o, 64);
+    const int oi = __shfl_xor(amax, o, 64);
+    if (ov > mx || (ov == mx && oi < amax)) { mx = ov; amax = oi; }
+    cnt += __shfl_xor(cnt, o, 64);
+  }
+  const int w = threadIdx.x >> 6, l = threadIdx.x & 63, nw = blockDim.x >> 6;
+  if (l == 0) { sred[w] = mx; sidx[w] = amax; scnt[w] = cnt; }
+  __syncthreads();
+  mx = sred[0]; amax = sidx[0]; cnt = scnt[0];
+  for (int i = 1; i < nw; ++i) {
+    if (sred[i] > mx || (sred[i] == mx && sidx[i] < amax)) { mx = sred[i]; amax = sidx[i]; }
+    cnt += scnt[i];
+  }
+  __syncthreads();
+  float se = 0.f, sz = 0.f;
+#pragma unroll
+  for (int i = 0; i < iters; ++i) {
+    const int j = threadIdx.x + 256 * i;
+    if (j < ncls) {
+      const float d = at(i, j) - mx;
+      se += __expf(d);
+      sz += d;
+    }
+  }
+  se = wave_sum(se);
+  sz = wave_sum(sz);
+  if (l == 0) { sred[w] = se; ssum[w] = sz; }
+  __syncthreads();
+  se = 0.f; sz = 0.f;
+  for (int i = 0; i < nw; ++i) { se += sred[i]; sz += ssum[i]; }
+  const float inv = 1.f / se;
+  const float uni = smoothing / (float)ncls, hot = 1.f - smoothing;
+#pragma unroll
+  for (int i = 0; i < iters; ++i) {
+    const int j = threadIdx.x + 256 * i;
+    if (j < ncls) {
+      const float p = __expf(at(i, j) - mx) * inv;
+      if (probs) probs[(size_t)n * ncls + j] = p;
+      if (dlogits) dlogits[(size_t)n * ncls + j] = (p - (j == y ? hot : 0.f) - uni) * grad_scale;
+    }
+  }
+  if (threadIdx.x == 0) {
+    // eps = 0: softmax_xent_kernel's own expression (the same bits; and no 0 * inf from a -inf logit)
+    loss[n] = smoothing == 0.f ? (mx + __logf(se)) - zy : __logf(se) - hot * (zy - mx) - uni * sz;
+    if (correct) correct[n] = (amax == y) ? 1 : 0;
+    if (correct_k) correct_k[n] = (zy == zy && cnt < top_k) ? 1 : 0;
+  }
+}
+
 // column sums: out[j] = scale * sum_n in[n][j]  (dense bias gradient)
 // Column sums (the dense bias gradient, sum over the batch of dlogits): a block covers 32
 // columns with 8 row slices of 32 lanes (coalesced 128-byte row segments, 4 independent loads
@@ -271,6 +373,18 @@ DRN_API int drn_softmax_xent(const float* logits, const int* labels, int N, int 
                              float* dlogits, float* loss, float* probs, int* correct, hipStream_t s) {
   drn::launch(drn::softmax_xent_kernel, dim3(N), dim3(256), 0, s, logits, labels, ncls, grad_scale, dlogits,
                      loss, probs, correct);
+  return (int)hipGetLastError();
+}
+
+// drn_softmax_xent with label smoothing (0 <= smoothing < 1) and a top-k count (top_k >= 1):
+// dlogits, probs, correct and correct_k may each be null.
+DRN_API int drn_softmax_xent_ex(const float* logits, const int* labels, int N, int ncls, float grad_scale,
+                                float smoothing, int top_k, float* dlogits, float* loss, float* probs, int* correct,
+                                int* correct_k, hipStream_t s) {
+  if (!(smoothing >= 0.f && smoothing < 1.f) || top_k < 1 || N < 1 || ncls < 1) return (int)hipErrorInvalidValue;
+  auto kern = ncls <= 256 * drn::XENT_REG_ROW ? drn::softmax_xent_ex_kernel<true> : drn::softmax_xent_ex_kernel<false>;
+  drn::launch(kern, dim3(N), dim3(256), 0, s, logits, labels, ncls, grad_scale, smoothing, top_k, dlogits, loss,
+                     probs, correct, correct_k);
   return (int)hipGetLastError();
 }
 

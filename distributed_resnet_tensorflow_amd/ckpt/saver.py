@@ -164,3 +164,16 @@ class Saver:
     @staticmethod
     def restore(prefix: str) -> Dict[str, np.ndarray]:
         return read_bundle(prefix)
+
+    @staticmethod
+    def restore_meta(prefix: str) -> dict:
+        """The checkpoint's `.meta` model description with the keys later versions added filled in
+        (label_smoothing: 0, what every checkpoint without the key was trained with); {} plus those
+        defaults when the file is missing or unreadable."""
+        try:
+            with open(prefix + ".meta") as f:
+                meta = dict(json.load(f))
+        except (OSError, ValueError):
+            meta = {}
+        meta["label_smoothing"] = float(meta.get("label_smoothing", 0.0))
+        return meta

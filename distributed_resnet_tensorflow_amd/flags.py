@@ -159,6 +159,10 @@ def validate(fv: "FlagValues") -> None:
     if fv.optimizer == "lars" and fv.optimizer_sharding:
         raise FlagsError("--optimizer=lars cannot be combined with --optimizer_sharding: a sharded update cuts "
                          "tensors across ranks and LARS needs each tensor's whole norm")
+    if not 0.0 <= fv.label_smoothing < 1.0:
+        raise FlagsError(f"--label_smoothing must be in [0, 1), got {fv.label_smoothing!r}")
+    if fv.top_k < 0:
+        raise FlagsError(f"--top_k must be >= 0, got {fv.top_k!r}")
 
 
 FLAGS = FlagValues()
@@ -253,6 +257,11 @@ def define_reference_flags(flag_values: FlagValues = FLAGS, **defaults) -> FlagV
     I("warmup_steps", 0, "--lr_policy=poly: linear warm-up steps.", fv)
     Fl("poly_power", 2.0, "--lr_policy=poly: power of the polynomial decay.", fv)
     Fl("end_lr", 0.0, "--lr_policy=poly: learning rate at --train_steps.", fv)
+    Fl("label_smoothing", 0.0, "Train against the target (1 - eps) one-hot + eps / num_classes (0 <= eps < 1; the "
+       "large-batch ImageNet recipes use 0.1). The logged loss is then the smoothed one; evaluation loss stays "
+       "the plain cross-entropy.", fv)
+    I("top_k", 0, "k >= 2: also count labels among the k largest logits (precision@k in logs, summaries and the "
+      "evaluator; ImageNet results are reported at k = 5). 0 or 1: top-1 only.", fv)
     I("collective_timeout_secs", 600, "Process-group timeout and collective-watchdog limit: a rank whose "
       "gradient exchange stalls this long exits (the launcher restarts the job from its checkpoint).", fv)
     I("fault_inject_step", -1, "Kill this process at the given global step (fault-injection tests).", fv)

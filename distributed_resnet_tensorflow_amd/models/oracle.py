@@ -67,9 +67,9 @@ def forward(spec: NetSpec, p: Dict[str, torch.Tensor], state: Dict[str, tuple], 
     return x @ p[f"{spec.dense_name}/kernel"] + p[f"{spec.dense_name}/bias"]
 
 
-def loss_fn(spec, p, state, images, labels, weight_decay=0.0, training=True):
+def loss_fn(spec, p, state, images, labels, weight_decay=0.0, training=True, label_smoothing=0.0):
     logits = forward(spec, p, state, images, training)
-    xent = F.cross_entropy(logits, labels.long())
+    xent = F.cross_entropy(logits, labels.long(), label_smoothing=label_smoothing)
     cost = xent
     if weight_decay:
         cost = xent + weight_decay * sum((v * v).sum() / 2 for v in p.values())

@@ -119,6 +119,7 @@ _SIGS = {
     "drn_sgemm": ([c_int, c_int, c_int, c_int, c_int, c_f, c_p, c_int, c_p, c_int, c_f, c_p, c_int, c_p, c_int, c_p,
                    c_p], c_int),
     "drn_softmax_xent": ([c_p, c_p, c_int, c_int, c_f, c_p, c_p, c_p, c_p, c_p], c_int),
+    "drn_softmax_xent_ex": ([c_p, c_p, c_int, c_int, c_f, c_f, c_int, c_p, c_p, c_p, c_p, c_p, c_p], c_int),
     "drn_colsum": ([c_p, c_int, c_int, c_p, c_f, c_int, c_p], c_int),
     "drn_maxpool_fwd": ([c_p, c_p, c_p] + [c_int] * 10 + [c_p, c_int, c_p], c_int),
     "drn_maxpool_bwd": ([c_p, c_p, c_p] + [c_int] * 10 + [c_p], c_int),

@@ -12,7 +12,7 @@ Op contract (NHWC activations, KRSC conv weights, fp32 statistics):
   conv_wgrad(x, dy, out, g, in_bn, relu_in, ws, splits)      out = dW (fp32, KRSC)
   bn_stats / bn_finalize / bn_inference / bn_apply
   bn_bwd_reduce / bn_finalize_bwd / bn_bwd_apply
-  pool_bnrelu, sgemm, softmax_xent, colsum, maxpool_fwd/bwd, sgd_momentum, weight_tflip
+  pool_bnrelu, sgemm, softmax_xent(_ex), colsum, maxpool_fwd/bwd, sgd_momentum, weight_tflip
 where pre(x) = relu(x * scale + shift) when in_bn = (scale, shift) is given.
 """
 from __future__ import annotations
@@ -891,6 +891,22 @@ class HipBackend(_Common):
                                            _ptr(dlogits), loss.data_ptr(), _ptr(probs), _ptr(correct),
                                            self.stream()), "drn_softmax_xent")
 
+    def softmax_xent_ex(self, logits, labels, grad_scale, dlogits, loss, correct, probs=None, smoothing=0.0, top_k=1,
+                        correct_k=None):
+        """softmax_xent against the smoothed target (1 - smoothing) [j == y] + smoothing / ncls, plus
+        correct_k[n] = the label is among the top_k logits (rank = #{z_j > z_y} + #{j < y: z_j == z_y});
+        one launch (head.hip softmax_xent_ex_kernel). dlogits, correct, probs, correct_k may be None."""
+        N, ncls = logits.shape
+        assert logits.dtype == loss.dtype == torch.float32 and labels.dtype == torch.int32
+        assert logits.is_contiguous() and labels.numel() == N and loss.numel() == N
+        for t, dt, n in ((dlogits, torch.float32, N * ncls), (probs, torch.float32, N * ncls),
+                         (correct, torch.int32, N), (correct_k, torch.int32, N)):
+            assert t is None or (t.dtype == dt and t.numel() == n and t.is_contiguous())
+        _lib.check(self.L.drn_softmax_xent_ex(logits.data_ptr(), labels.data_ptr(), N, ncls, float(grad_scale),
+                                              float(smoothing), int(top_k), _ptr(dlogits), loss.data_ptr(),
+                                              _ptr(probs), _ptr(correct), _ptr(correct_k), self.stream()),
+                   "drn_softmax_xent_ex")
+
     def colsum(self, x, out, scale=1.0, accumulate=False):
         rows, cols = x.shape
         _lib.check(self.L.drn_colsum(x.data_ptr(), rows, cols, out.data_ptr(), float(scale), int(accumulate),
@@ -1226,6 +1242,37 @@ class RefBackend(_Common):
             dlogits.copy_((p - oh) * grad_scale)
         if correct is not None:
             correct.copy_((logits.argmax(1) == lab).int())
+
+    def softmax_xent_ex(self, logits, labels, grad_scale, dlogits, loss, correct, probs=None, smoothing=0.0, top_k=1,
+                        correct_k=None):
+        """HipBackend.softmax_xent_ex's contract in torch, in the reference dtype (the oracle: fp64
+        under RefBackend(dtype=torch.float64)). The rank is taken on the logits as given (no
+        upcast: ties stay ties)."""
+        if not 0.0 <= smoothing < 1.0 or top_k < 1:
+            raise ValueError(f"softmax_xent_ex needs 0 <= smoothing < 1 and top_k >= 1, got {smoothing}, {top_k}")
+        K = logits.shape[1]
+        lab = labels.long()
+        z = logits.to(_DT[0])
+        d = z - z.max(1, keepdim=True)[0]
+        e = d.exp()
+        se = e.sum(1)
+        ls = se.log() - (1.0 - smoothing) * d.gather(1, lab[:, None])[:, 0]
+        if smoothing != 0.0:
+            ls = ls - (smoothing / K) * d.sum(1)
+        loss.copy_(ls)
+        p = e / se[:, None]
+        if probs is not None:
+            probs.copy_(p)
+        if dlogits is not None:
+            oh = F.one_hot(lab, K).to(_DT[0])
+            dlogits.copy_((p - (1.0 - smoothing) * oh - smoothing / K) * grad_scale)
+        if correct is not None:
+            correct.copy_((logits.argmax(1) == lab).int())
+        if correct_k is not None:
+            zy = logits.gather(1, lab[:, None])
+            before = torch.arange(K, device=logits.device)[None, :] < lab[:, None]
+            rank = (logits > zy).sum(1) + ((logits == zy) & before).sum(1)
+            correct_k.copy_(((rank < top_k) & ~torch.isnan(zy[:, 0])).int())
 
     def colsum(self, x, out, scale=1.0, accumulate=False):
         s = x.sum(0) * scale

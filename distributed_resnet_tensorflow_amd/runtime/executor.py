@@ -104,7 +104,7 @@ class Executor:
     def __init__(self, spec: NetSpec, batch: int, backend, device, seed: int = 0,
                  weight_decay: float = 2e-4, momentum: float = 0.9, params: ParamStore | None = None,
                  materialize_bn: Optional[bool] = None, optimizer: str = "momentum", lars_eta: float = 0.001,
-                 lars_eps: float = 1e-9):
+                 lars_eps: float = 1e-9, label_smoothing: float = 0.0, top_k: int = 0):
         self.spec, self.N, self.be = spec, batch, backend
         # "momentum": the reference's MomentumOptimizer; "lars": the same update with each conv /
         # dense kernel's gradient (weight decay included) scaled by its layer-wise trust ratio
@@ -112,6 +112,15 @@ class Executor:
         if optimizer not in ("momentum", "lars"):
             raise ValueError(f"optimizer must be 'momentum' or 'lars', got {optimizer!r}")
         self.optimizer, self.lars_eta, self.lars_eps = optimizer, float(lars_eta), float(lars_eps)
+        # label_smoothing: the training target is (1 - eps) one-hot + eps / num_classes; top_k >= 2:
+        # correct_k[n] = the label is among the k largest logits (0 / 1: top-1 only). Both come out
+        # of the head's one loss kernel (csrc/kernels/head.hip softmax_xent_ex_kernel); with the
+        # defaults the step calls softmax_xent as it always did
+        if not 0.0 <= label_smoothing < 1.0:
+            raise ValueError(f"label_smoothing must be in [0, 1), got {label_smoothing!r}")
+        if int(top_k) != top_k or top_k < 0:
+            raise ValueError(f"top_k must be an integer >= 0, got {top_k!r}")
+        self.label_smoothing, self.top_k = float(label_smoothing), int(top_k)
         # fuse each BN's backward reduction into the epilogue of the data-gradient conv feeding it
         self.fuse_bn_bwd = True
         # (The BN backward applied on load by both 1x1 consumers instead of materialised -- the
@@ -465,6 +474,7 @@ class Executor:
         self.dlogits = self._f32(N, ncls)
         self.loss_vec = self._f32(N)
         self.correct = torch.zeros(N, dtype=torch.int32, device=self.device)
+        self.correct_k = torch.zeros(N, dtype=torch.int32, device=self.device) if self.top_k >= 2 else None
         self.dpool = self._f32(N, C)
         self.dense_w = self.P.w(f"{sp.dense_name}/kernel")
         self.dense_b = self.P.w(f"{sp.dense_name}/bias")
@@ -630,8 +640,15 @@ class Executor:
         be.pool_bnrelu(self.last_out, fb.scale, fb.shift, self.pooled, relu=True)
         N, C, ncls = self.N, sp.final_c, sp.num_classes
         be.sgemm(0, 1, N, ncls, C, 1.0, self.pooled, C, self.dense_w, C, 0.0, self.logits, ncls, bias=self.dense_b)
-        be.softmax_xent(self.logits, self.labels, 1.0 / N, self.dlogits if train else None, self.loss_vec,
-                        self.correct)
+        # (evaluation loss is the plain cross-entropy: smoothing shapes the training target only)
+        smoothing = self.label_smoothing if train else 0.0
+        if smoothing == 0.0 and self.top_k < 2:
+            be.softmax_xent(self.logits, self.labels, 1.0 / N, self.dlogits if train else None, self.loss_vec,
+                            self.correct)
+        else:
+            be.softmax_xent_ex(self.logits, self.labels, 1.0 / N, self.dlogits if train else None, self.loss_vec,
+                               self.correct, smoothing=smoothing, top_k=max(self.top_k, 1),
+                               correct_k=self.correct_k)
         if self.check_nan:
             self._check(self.loss_vec, "cross-entropy")
 
@@ -1108,7 +1125,14 @@ class Executor:
     # metrics (host side, off the hot path)
     # ------------------------------------------------------------------------------------------
     def metrics(self) -> dict:
+        """Loss and precision of the last forward. After a training forward with label_smoothing > 0,
+        cross_entropy and cost are the smoothed loss (the objective being minimised), which is at
+        least the entropy of the smoothed target; an evaluation forward reports the plain
+        cross-entropy. precision_top_k is present only when top_k >= 2."""
         xent = float(self.loss_vec.double().mean())
         prec = float(self.correct.double().mean())
         l2 = float(self.P.trainable_l2())
-        return {"cross_entropy": xent, "cost": xent + self.wd * l2, "precision": prec}
+        m = {"cross_entropy": xent, "cost": xent + self.wd * l2, "precision": prec}
+        if self.correct_k is not None:
+            m["precision_top_k"] = float(self.correct_k.double().mean())
+        return m

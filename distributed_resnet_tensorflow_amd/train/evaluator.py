@@ -2,7 +2,9 @@
 resnet_imagenet_eval.py:154-210): restore the latest checkpoint in --log_root, run
 --eval_batch_count batches in inference mode (BN moving statistics), log
 `loss, precision, best precision`, write `Precision` / `Best Precision` summaries at the
-checkpoint's global step, sleep and repeat unless --eval_once.
+checkpoint's global step, sleep and repeat unless --eval_once. With --top_k=K (K >= 2) the top-K
+precision is accumulated beside it (`precision@K` in the log, `Precision@K` / `Best Precision@K`
+summaries, `precision_top_k` in the results and in best_precision.json); "best" stays top-1.
 
 Fixes of reference quirks: no busy-spin when there is no checkpoint (Q8), best precision
 persisted in eval_dir/best_precision.json across restarts (Q11), the eval set is read in order
@@ -28,9 +30,9 @@ from .trainer import WEIGHT_DECAY, apply_thread_flags, make_feeder, model_spec_f
 log = logging.getLogger("drn")
 
 
-def _load_best(path):
+def _load_best(path, key="best_precision"):
     try:
-        return float(json.load(open(path))["best_precision"])
+        return float(json.load(open(path))[key])
     except Exception:
         return 0.0
 
@@ -45,10 +47,14 @@ def evaluate(FLAGS, eval_batch_size: int = 100, max_evals: int = -1):
     cluster = cl.resolve(FLAGS, env={})
     spec = model_spec_from_flags(FLAGS)
     be = make_backend(cluster.device, getattr(FLAGS, "precision", "bf16"))
-    ex = Executor(spec, eval_batch_size, be, cluster.device, weight_decay=WEIGHT_DECAY.get(FLAGS.dataset, 1e-4))
+    top_k = int(getattr(FLAGS, "top_k", 0))
+    top_k = top_k if top_k >= 2 else 0  # K >= 2: precision@K beside precision ("best" stays top-1)
+    ex = Executor(spec, eval_batch_size, be, cluster.device, weight_decay=WEIGHT_DECAY.get(FLAGS.dataset, 1e-4),
+                  top_k=top_k)
     writer = EventFileWriter(FLAGS.eval_dir) if FLAGS.eval_dir else None
     best_path = os.path.join(FLAGS.eval_dir, "best_precision.json") if FLAGS.eval_dir else None
     best = _load_best(best_path) if best_path else 0.0
+    best_k = _load_best(best_path, "best_precision_top_k") if best_path and top_k else 0.0
     last = None
     n_eval = 0
     results = []
@@ -68,7 +74,7 @@ def evaluate(FLAGS, eval_batch_size: int = 100, max_evals: int = -1):
                 last = prefix
                 step = ex.P.global_step or step_of(prefix)
                 feeder = make_feeder(FLAGS, ex, cluster, False, batch=eval_batch_size)
-                total_loss, correct, total = 0.0, 0, 0
+                total_loss, correct, correct_k, total = 0.0, 0, 0, 0
                 try:
                     for _ in range(FLAGS.eval_batch_count):
                         if not feeder.next():
@@ -78,22 +84,35 @@ def evaluate(FLAGS, eval_batch_size: int = 100, max_evals: int = -1):
                         feeder.prefetch()   # host load of the next batch while this one runs
                         total_loss += float(ex.loss_vec[:v].double().sum())
                         correct += int(ex.correct[:v].sum())
+                        if top_k:
+                            correct_k += int(ex.correct_k[:v].sum())
                         total += v
                 finally:
                     feeder.close()
                 precision = correct / max(total, 1)
                 loss = total_loss / max(total, 1) + ex.wd * float(ex.P.trainable_l2())
                 best = max(best, precision)
+                scalars = {"Precision": precision, "Best Precision": best}
+                record = {"best_precision": best, "step": step}
+                result = {"step": step, "loss": loss, "precision": precision, "best_precision": best}
+                line = "loss: %.3f, precision: %.3f, best precision: %.3f" % (loss, precision, best)
+                if top_k:
+                    precision_k = correct_k / max(total, 1)
+                    best_k = max(best_k, precision_k)
+                    scalars.update({f"Precision@{top_k}": precision_k, f"Best Precision@{top_k}": best_k})
+                    record.update({"precision_top_k": precision_k, "best_precision_top_k": best_k, "top_k": top_k})
+                    result["precision_top_k"] = precision_k
+                    line += ", precision@%d: %.3f" % (top_k, precision_k)
                 if writer is not None:
-                    writer.add_scalars(step, {"Precision": precision, "Best Precision": best})
+                    writer.add_scalars(step, scalars)
                     writer.flush()
                 if best_path:
                     tmp = best_path + ".tmp"
                     with open(tmp, "w") as f:
-                        json.dump({"best_precision": best, "step": step}, f)
+                        json.dump(record, f)
                     os.replace(tmp, best_path)
-                log.info("loss: %.3f, precision: %.3f, best precision: %.3f", loss, precision, best)
-                results.append({"step": step, "loss": loss, "precision": precision, "best_precision": best})
+                log.info("%s", line)
+                results.append(result)
                 n_eval += 1
         if FLAGS.eval_once and last is not None:
             break

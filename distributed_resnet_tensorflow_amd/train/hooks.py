@@ -2,9 +2,9 @@
 
   LoggingHook     LoggingTensorHook: step / loss / precision / lr every N steps (CIFAR 20,
                   ImageNet 40) + throughput (images/sec, steps/sec) — the reference has no timer
-                  (SURVEY Q17); optional metrics.jsonl.
+                  (SURVEY Q17); optional metrics.jsonl. --top_k=K adds `precision@K`.
   SummaryHook     SummarySaverHook(save_steps=100): cross_entropy, cost, learning_rate,
-                  Precision (+ images/sec) as tfevents (chief only).
+                  Precision (+ images/sec; + Precision@K with --top_k=K) as tfevents (chief only).
   CheckpointHook  MonitoredTrainingSession(save_checkpoint_secs=60) saver (chief only).
   StopAtStepHook  StopAtStepHook(last_step=train_steps) (the reference CIFAR main never stops:
                   SURVEY Q5; here --train_steps is honoured).
@@ -41,6 +41,11 @@ class Hook:
         return False
 
 
+def _top_k(sess) -> int:
+    """The K of the session's precision_top_k metric (Executor(top_k=K))."""
+    return int(getattr(getattr(sess, "ex", None), "top_k", 0))
+
+
 class LoggingHook(Hook):
     def __init__(self, every_n: int, batch_per_step: int, metrics_path: Optional[str] = None, with_lr: bool = True,
                  world: int = 1):
@@ -67,6 +72,8 @@ class LoggingHook(Hook):
         m["images_per_sec_per_gpu"] = m["images_per_sec"] / self.world
         self._t, self._s = now, step
         parts = [f"step = {step}", f"loss = {m['cost']:.5f}", f"precision = {m['precision']:.5f}"]
+        if "precision_top_k" in m:  # (--top_k >= 2 only: the default line is unchanged)
+            parts.append(f"precision@{_top_k(sess)} = {m['precision_top_k']:.5f}")
         if self.with_lr:
             parts.append(f"lr = {m['learning_rate']:.5g}")
         parts.append(f"({m['steps_per_sec']:.2f} steps/sec, {m['images_per_sec']:.1f} images/sec)")
@@ -90,6 +97,8 @@ class SummaryHook(Hook):
         m = metrics_fn()
         scalars = {"cross_entropy": m["cross_entropy"], "cost": m["cost"],
                    "learning_rate": m["learning_rate"], "Precision": m["precision"]}
+        if "precision_top_k" in m:
+            scalars[f"Precision@{_top_k(sess)}"] = m["precision_top_k"]
         ex = getattr(sess, "ex", None)
         if getattr(ex, "optimizer", "momentum") == "lars":
             # the last update's trust ratios of the adapting (conv / dense kernel) slots

@@ -79,13 +79,14 @@ class TrainingSession:
                  bucket_mb: float = 25.0, meta: Optional[dict] = None, allreduce: str = "rccl", wire: str = "fp32",
                  collective_timeout_s: float = 0.0, precision: str = "bf16", shard_optimizer: bool = False,
                  step_trial: bool = True, optimizer: str = "momentum", lars_eta: float = 0.001,
-                 lars_eps: float = 1e-9):
+                 lars_eps: float = 1e-9, label_smoothing: float = 0.0, top_k: int = 0):
         self.cluster = cluster
         self.spec = spec
         self.device = torch.device(cluster.device)
         self.be = make_backend(cluster.device, precision)
         self.ex = Executor(spec, batch, self.be, self.device, seed=seed, weight_decay=weight_decay,
-                           optimizer=optimizer, lars_eta=lars_eta, lars_eps=lars_eps)
+                           optimizer=optimizer, lars_eta=lars_eta, lars_eps=lars_eps,
+                           label_smoothing=label_smoothing, top_k=top_k)
         self.lr = lr_schedule
         self.meta = meta or {}
         # DRN_FORCE_DP=1: the data-parallel engine on a single-rank process group (profiling the
@@ -201,6 +202,10 @@ class TrainingSession:
             self.data_state = import_state(self.ex, tensors)
             self.restored_from = prefix
             log.info("Restored %s (global_step %d)", prefix, self.ex.P.global_step)
+            was = Saver.restore_meta(prefix)["label_smoothing"]
+            if was != self.ex.label_smoothing:
+                log.warning("checkpoint was trained with label_smoothing %g, continuing with %g", was,
+                            self.ex.label_smoothing)
         if self.engine is not None:
             self.engine.broadcast_parameters()
             if self.cluster.is_chief is False:

@@ -53,7 +53,8 @@ def _meta(FLAGS, spec):
             "width_multiplier": FLAGS.width_multiplier if FLAGS.model == "wide_resnet" else 1,
             "num_classes": spec.num_classes,
             "spec_name": spec.name,
-            "optimizer": FLAGS.optimizer, "eta": FLAGS.lars_eta, "eps": FLAGS.lars_eps}
+            "optimizer": FLAGS.optimizer, "eta": FLAGS.lars_eta, "eps": FLAGS.lars_eps,
+            "label_smoothing": FLAGS.label_smoothing}
 
 
 def make_feeder(FLAGS, ex, cluster, is_training: bool, data_state=None, batch=None):
@@ -109,7 +110,8 @@ def train(FLAGS, cluster=None):
                            meta=_meta(FLAGS, spec), allreduce=FLAGS.allreduce, wire=FLAGS.allreduce_wire,
                            collective_timeout_s=FLAGS.collective_timeout_secs, precision=FLAGS.precision,
                            shard_optimizer=FLAGS.optimizer_sharding, optimizer=FLAGS.optimizer,
-                           lars_eta=FLAGS.lars_eta, lars_eps=FLAGS.lars_eps)
+                           lars_eta=FLAGS.lars_eta, lars_eps=FLAGS.lars_eps,
+                           label_smoothing=FLAGS.label_smoothing, top_k=FLAGS.top_k)
     feeder = make_feeder(FLAGS, sess.ex, cluster, True, sess.data_state)
     is_imagenet = FLAGS.dataset == "imagenet"
     hooks = [LoggingHook(FLAGS.log_every_n_steps, FLAGS.batch_size * cluster.world,
