@@ -246,6 +246,171 @@ __global__ __launch_bounds__(256) void lars_update_kernel(float* __restrict__ w,
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Weight EMA (tf.train.ExponentialMovingAverage): ema <- ema - (1 - d) * (ema - w_new), applied to
+// the freshly updated fp32 weight while it is still in a register -- one more read-modify-write
+// stream in the optimizer's pass instead of a separate pass re-reading the master buffer. The decay
+// d is read from device memory like the learning rate, so a captured graph / recorded plan replays
+// with the warm-up value the host wrote for that step. These are kernels of their own (the update
+// arithmetic repeats sgd_momentum_kernel / lars_update_kernel statement for statement, so w, m and
+// wb come out bit-identical): with the EMA off a step launches exactly the kernels above, whose
+// code these leave untouched.
+__device__ __forceinline__ void ema1(float& e, float wv, float om) { e -= om * (e - wv); }
+__device__ __forceinline__ void ema4(float4& e, const float4& wv, float om) {
+  ema1(e.x, wv.x, om); ema1(e.y, wv.y, om); ema1(e.z, wv.z, om); ema1(e.w, wv.w, om);
+}
+
+template <typename G>
+__global__ __launch_bounds__(256) void sgd_momentum_ema_kernel(float* __restrict__ w, float* __restrict__ m,
+                                                               const G* __restrict__ g, bf16_t* __restrict__ wb,
+                                                               int64_t n4, const float* __restrict__ lr_ptr, float mu,
+                                                               float wd, float grad_scale,
+                                                               const int* __restrict__ skip, float* __restrict__ ema,
+                                                               const float* __restrict__ decay_ptr) {
+  if (skip != nullptr && *skip != 0) return;  // the average is skipped with the update
+  const float lr = *lr_ptr;
+  const float om = 1.f - *decay_ptr;
+  auto upd = [&](float4& wv, float4& mv, const float4& gv) {
+    float gg;
+    gg = gv.x * grad_scale + wd * wv.x; mv.x = mu * mv.x + gg; wv.x -= lr * mv.x;
+    gg = gv.y * grad_scale + wd * wv.y; mv.y = mu * mv.y + gg; wv.y -= lr * mv.y;
+    gg = gv.z * grad_scale + wd * wv.z; mv.z = mu * mv.z + gg; wv.z -= lr * mv.z;
+    gg = gv.w * grad_scale + wd * wv.w; mv.w = mu * mv.w + gg; wv.w -= lr * mv.w;
+  };
+  auto store = [&](int64_t i, const float4& wv, const float4& mv, const float4& ev) {
+    reinterpret_cast<float4*>(w)[i] = wv;
+    reinterpret_cast<float4*>(m)[i] = mv;
+    reinterpret_cast<float4*>(ema)[i] = ev;
+    if (wb) {
+      uint2 o;
+      o.x = pack2bf(wv.x, wv.y);
+      o.y = pack2bf(wv.z, wv.w);
+      reinterpret_cast<uint2*>(wb)[i] = o;
+    }
+  };
+  // two float4 groups in flight per thread (4 streams read, 4 written)
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  for (; i + stride < n4; i += 2 * stride) {
+    float4 w0 = reinterpret_cast<float4*>(w)[i], w1 = reinterpret_cast<float4*>(w)[i + stride];
+    float4 m0 = reinterpret_cast<float4*>(m)[i], m1 = reinterpret_cast<float4*>(m)[i + stride];
+    float4 e0 = reinterpret_cast<float4*>(ema)[i], e1 = reinterpret_cast<float4*>(ema)[i + stride];
+    const float4 g0 = grad4(g, i), g1 = grad4(g, i + stride);
+    upd(w0, m0, g0);
+    upd(w1, m1, g1);
+    ema4(e0, w0, om);
+    ema4(e1, w1, om);
+    store(i, w0, m0, e0);
+    store(i + stride, w1, m1, e1);
+  }
+  if (i < n4) {
+    float4 w0 = reinterpret_cast<float4*>(w)[i];
+    float4 m0 = reinterpret_cast<float4*>(m)[i];
+    float4 e0 = reinterpret_cast<float4*>(ema)[i];
+    const float4 g0 = grad4(g, i);
+    upd(w0, m0, g0);
+    ema4(e0, w0, om);
+    store(i, w0, m0, e0);
+  }
+}
+
+// lars_update_kernel + the EMA of the updated slots (ema: the base of a flat buffer in w's layout)
+template <typename G>
+__global__ __launch_bounds__(256) void lars_update_ema_kernel(float* __restrict__ w, float* __restrict__ m,
+                                                              const G* __restrict__ g, bf16_t* __restrict__ wb,
+                                                              const LarsSlot* __restrict__ table, int first_slot,
+                                                              int nslots, const float* __restrict__ partials,
+                                                              float* __restrict__ trust_out,
+                                                              const float* __restrict__ lr_ptr, float mu, float wd,
+                                                              float grad_scale, float eta, float eps,
+                                                              const int* __restrict__ skip, float* __restrict__ ema,
+                                                              const float* __restrict__ decay_ptr) {
+  __shared__ float red[8];
+  if (skip != nullptr && *skip != 0) return;
+  const float lr = *lr_ptr;
+  const float om = 1.f - *decay_ptr;
+  const int64_t b0 = table[first_slot].begin, b1 = table[first_slot + nslots].begin;
+  for (int64_t b = b0 + blockIdx.x; b < b1; b += gridDim.x) {
+    const int slot = lars_find(table, first_slot, nslots, b);
+    const LarsSlot d = table[slot];
+    const int c = (int)(b - d.begin);
+    float trust = 1.f;
+    if (d.adapt) {
+      const int nchunk = (int)(table[slot + 1].begin - d.begin);
+      float sw = 0.f, sg = 0.f;
+      for (int j = threadIdx.x; j < nchunk; j += 256) {
+        sw += partials[2 * (d.begin + j)];
+        sg += partials[2 * (d.begin + j) + 1];
+      }
+      lars_block_sum(sw, sg, red);
+      if (sw > 0.f && sg > 0.f) {
+        const float wn = sqrtf(sw), gn = sqrtf(sg);
+        trust = eta * wn / (gn + wd * wn + eps);
+      }
+    }
+    if (c == 0 && threadIdx.x == 0) trust_out[slot] = trust;
+    auto upd1 = [&](float& wv, float& mv, float gv) {
+      const float gg = trust * (gv * grad_scale + wd * wv);
+      mv = __builtin_fmaf(mu, mv, gg);
+      wv -= lr * mv;
+    };
+    auto upd = [&](float4& wv, float4& mv, const float4& gv) {
+      upd1(wv.x, mv.x, gv.x); upd1(wv.y, mv.y, gv.y); upd1(wv.z, mv.z, gv.z); upd1(wv.w, mv.w, gv.w);
+    };
+    auto store = [&](int64_t i, const float4& wv, const float4& mv, const float4& ev) {
+      reinterpret_cast<float4*>(w)[i] = wv;
+      reinterpret_cast<float4*>(m)[i] = mv;
+      reinterpret_cast<float4*>(ema)[i] = ev;
+      if (wb) {
+        uint2 o;
+        o.x = pack2bf(wv.x, wv.y);
+        o.y = pack2bf(wv.z, wv.w);
+        reinterpret_cast<uint2*>(wb)[i] = o;
+      }
+    };
+    const int64_t base4 = d.offset / 4;
+    const int full4 = d.numel >> 2;
+    const int i0 = c * LARS_CHUNK4;
+    const int i1 = min(i0 + LARS_CHUNK4, full4);
+    int i = i0 + threadIdx.x;
+    for (; i + 256 < i1; i += 512) {
+      const int64_t p = base4 + i, q = p + 256;
+      float4 w0 = reinterpret_cast<float4*>(w)[p], w1 = reinterpret_cast<float4*>(w)[q];
+      float4 m0 = reinterpret_cast<float4*>(m)[p], m1 = reinterpret_cast<float4*>(m)[q];
+      float4 e0 = reinterpret_cast<float4*>(ema)[p], e1 = reinterpret_cast<float4*>(ema)[q];
+      const float4 g0 = grad4(g, p), g1 = grad4(g, q);
+      upd(w0, m0, g0);
+      upd(w1, m1, g1);
+      ema4(e0, w0, om);
+      ema4(e1, w1, om);
+      store(p, w0, m0, e0);
+      store(q, w1, m1, e1);
+    }
+    if (i < i1) {
+      const int64_t p = base4 + i;
+      float4 w0 = reinterpret_cast<float4*>(w)[p];
+      float4 m0 = reinterpret_cast<float4*>(m)[p];
+      float4 e0 = reinterpret_cast<float4*>(ema)[p];
+      const float4 g0 = grad4(g, p);
+      upd(w0, m0, g0);
+      ema4(e0, w0, om);
+      store(p, w0, m0, e0);
+    }
+    if (threadIdx.x == 0 && (full4 << 2) < d.numel && i0 + LARS_CHUNK4 > full4 && i0 <= full4) {
+      for (int e = full4 << 2; e < d.numel; ++e) {
+        const int64_t p = d.offset + e;
+        float wv = w[p], mv = m[p], ev = ema[p];
+        upd1(wv, mv, grad1(g, p));
+        ema1(ev, wv, om);
+        w[p] = wv;
+        m[p] = mv;
+        ema[p] = ev;
+        if (wb) wb[p] = f2bf(wv);
+      }
+    }
+  }
+}
+
 __global__ __launch_bounds__(256) void cast_bf16_kernel(const float* __restrict__ x, bf16_t* __restrict__ y,
                                                         int64_t n4) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
@@ -373,6 +538,46 @@ DRN_API int drn_lars_momentum(float* w, float* m, const void* g, int g_bf16, voi
                 nslots, partials, grad_scale, skip);
     drn::launch(drn::lars_update_kernel<float>, grid, block, 0, s, w, m, (const float*)g, (bf16_t*)w_bf16, t,
                 first_slot, nslots, (const float*)partials, trust, lr_ptr, momentum, wd, grad_scale, eta, eps, skip);
+  }
+  return (int)hipGetLastError();
+}
+
+// drn_sgd_momentum + the weight EMA in the same launch: ema (n floats, 16-byte aligned like w) <-
+// ema - (1 - *decay_ptr) * (ema - w_new); decay_ptr is a device float. Untouched when *skip != 0.
+DRN_API int drn_sgd_momentum_ema(float* w, float* m, const void* g, int g_bf16, void* w_bf16, int64_t n,
+                                 const float* lr_ptr, float momentum, float wd, float grad_scale, const int* skip,
+                                 float* ema, const float* decay_ptr, hipStream_t s) {
+  if (n % 4 || ema == nullptr || decay_ptr == nullptr) return (int)hipErrorInvalidValue;
+  if (g_bf16)
+    drn::launch(drn::sgd_momentum_ema_kernel<bf16_t>, dim3(drn::grid_for(n / 4)), dim3(256), 0, s, w, m,
+                (const bf16_t*)g, (bf16_t*)w_bf16, n / 4, lr_ptr, momentum, wd, grad_scale, skip, ema, decay_ptr);
+  else
+    drn::launch(drn::sgd_momentum_ema_kernel<float>, dim3(drn::grid_for(n / 4)), dim3(256), 0, s, w, m,
+                (const float*)g, (bf16_t*)w_bf16, n / 4, lr_ptr, momentum, wd, grad_scale, skip, ema, decay_ptr);
+  return (int)hipGetLastError();
+}
+
+// drn_lars_momentum + the weight EMA in its update pass (the norms pass is the same kernel): ema is
+// the base of a flat buffer in w's layout, decay_ptr a device float, as in drn_sgd_momentum_ema.
+DRN_API int drn_lars_momentum_ema(float* w, float* m, const void* g, int g_bf16, void* w_bf16, const void* table,
+                                  int first_slot, int nslots, float* partials, float* trust, const float* lr_ptr,
+                                  float momentum, float wd, float grad_scale, float eta, float eps, const int* skip,
+                                  float* ema, const float* decay_ptr, hipStream_t s) {
+  if (first_slot < 0 || nslots < 1 || ema == nullptr || decay_ptr == nullptr) return (int)hipErrorInvalidValue;
+  const drn::LarsSlot* t = (const drn::LarsSlot*)table;
+  const dim3 grid(drn::LARS_GRID), block(256);
+  if (g_bf16) {
+    drn::launch(drn::lars_norms_kernel<bf16_t>, grid, block, 0, s, (const float*)w, (const bf16_t*)g, t, first_slot,
+                nslots, partials, grad_scale, skip);
+    drn::launch(drn::lars_update_ema_kernel<bf16_t>, grid, block, 0, s, w, m, (const bf16_t*)g, (bf16_t*)w_bf16, t,
+                first_slot, nslots, (const float*)partials, trust, lr_ptr, momentum, wd, grad_scale, eta, eps, skip,
+                ema, decay_ptr);
+  } else {
+    drn::launch(drn::lars_norms_kernel<float>, grid, block, 0, s, (const float*)w, (const float*)g, t, first_slot,
+                nslots, partials, grad_scale, skip);
+    drn::launch(drn::lars_update_ema_kernel<float>, grid, block, 0, s, w, m, (const float*)g, (bf16_t*)w_bf16, t,
+                first_slot, nslots, (const float*)partials, trust, lr_ptr, momentum, wd, grad_scale, eta, eps, skip,
+                ema, decay_ptr);
   }
   return (int)hipGetLastError();
 }

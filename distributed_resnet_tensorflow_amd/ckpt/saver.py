@@ -7,8 +7,8 @@ resnet_cifar_main_horovod.py:311), keeps the last 5 (Saver max_to_keep), restore
 (re)start; the eval poller reads `log_root/checkpoint` (resnet_cifar_eval.py:100-109).
 
 Saved variables use TF names and layouts (runtime/params.py: to_tf): every trainable variable,
-its `<name>/Momentum` slot, BN `moving_mean`/`moving_variance`, `global_step` (int64), plus
-`drn/*` data-iterator state. A `.meta` file is written as a small JSON model description (NOT
+its `<name>/Momentum` slot (and, with --ema_decay, its `<name>/ExponentialMovingAverage` shadow),
+BN `moving_mean`/`moving_variance`, `global_step` (int64), plus `drn/*` data-iterator state. A `.meta` file is written as a small JSON model description (NOT
 a TF MetaGraphDef: there is no graph to serialise). Writes go to temporary names and are
 renamed into place; the state file is replaced last, so a crash never leaves a state file
 pointing at a partial checkpoint.
@@ -168,12 +168,13 @@ class Saver:
     @staticmethod
     def restore_meta(prefix: str) -> dict:
         """The checkpoint's `.meta` model description with the keys later versions added filled in
-        (label_smoothing: 0, what every checkpoint without the key was trained with); {} plus those
-        defaults when the file is missing or unreadable."""
+        (label_smoothing: 0 and ema_decay: 0, what every checkpoint without the key was trained
+        with); {} plus those defaults when the file is missing or unreadable."""
         try:
             with open(prefix + ".meta") as f:
                 meta = dict(json.load(f))
         except (OSError, ValueError):
             meta = {}
         meta["label_smoothing"] = float(meta.get("label_smoothing", 0.0))
+        meta["ema_decay"] = float(meta.get("ema_decay", 0.0))
         return meta

@@ -163,6 +163,10 @@ def validate(fv: "FlagValues") -> None:
         raise FlagsError(f"--label_smoothing must be in [0, 1), got {fv.label_smoothing!r}")
     if fv.top_k < 0:
         raise FlagsError(f"--top_k must be >= 0, got {fv.top_k!r}")
+    if not 0.0 <= fv.ema_decay < 1.0:
+        raise FlagsError(f"--ema_decay must be in [0, 1), got {fv.ema_decay!r}")
+    if fv.ema_decay > 0 and fv.model == "lrnet":
+        raise FlagsError("--ema_decay is not supported by --model=lrnet (its Adam path keeps no weight average)")
 
 
 FLAGS = FlagValues()
@@ -262,6 +266,13 @@ def define_reference_flags(flag_values: FlagValues = FLAGS, **defaults) -> FlagV
        "the plain cross-entropy.", fv)
     I("top_k", 0, "k >= 2: also count labels among the k largest logits (precision@k in logs, summaries and the "
       "evaluator; ImageNet results are reported at k = 5). 0 or 1: top-1 only.", fv)
+    Fl("ema_decay", 0.0, "d > 0: keep an exponential moving average of every trainable variable "
+       "(tf.train.ExponentialMovingAverage: ema -= (1 - d) * (ema - w) after each update, fused into the optimizer "
+       "kernels), checkpointed as <var>/ExponentialMovingAverage; 0 <= d < 1, 0 = off.", fv)
+    B("ema_warmup", True, "TF's num_updates form of the average: update t uses min(ema_decay, (1 + t) / (10 + t)).",
+      fv)
+    B("eval_ema", False, "--mode=eval: evaluate the checkpoint's <var>/ExponentialMovingAverage tensors in place of "
+      "the variables (an error if it was trained without --ema_decay).", fv)
     I("collective_timeout_secs", 600, "Process-group timeout and collective-watchdog limit: a rank whose "
       "gradient exchange stalls this long exits (the launcher restarts the job from its checkpoint).", fv)
     I("fault_inject_step", -1, "Kill this process at the given global step (fault-injection tests).", fv)

@@ -126,6 +126,10 @@ _SIGS = {
     "drn_sgd_momentum": ([c_p, c_p, c_p, c_int, c_p, c_i64, c_p, c_f, c_f, c_f, c_p, c_p], c_int),
     "drn_lars_momentum": ([c_p, c_p, c_p, c_int, c_p, c_p, c_int, c_int, c_p, c_p, c_p, c_f, c_f, c_f, c_f, c_f,
                            c_p, c_p], c_int),
+    # ... + the weight EMA in the same launch: the plain signatures + (ema, decay_ptr) before the stream
+    "drn_sgd_momentum_ema": ([c_p, c_p, c_p, c_int, c_p, c_i64, c_p, c_f, c_f, c_f, c_p, c_p, c_p, c_p], c_int),
+    "drn_lars_momentum_ema": ([c_p, c_p, c_p, c_int, c_p, c_p, c_int, c_int, c_p, c_p, c_p, c_f, c_f, c_f, c_f, c_f,
+                               c_p, c_p, c_p, c_p], c_int),
     "drn_lars_slot_size": ([], c_int),
     "drn_lars_chunk": ([], c_int),
     "drn_cast_bf16": ([c_p, c_p, c_i64, c_p], c_int),

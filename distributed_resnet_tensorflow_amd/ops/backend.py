@@ -928,20 +928,33 @@ class HipBackend(_Common):
                                           pad_h, pad_w, self.stream()), "drn_maxpool_bwd")
 
     # -- optimizer / weights ------------------------------------------------------------------------
-    def sgd_momentum(self, w, m, g, wb, lr_t, momentum, wd, grad_scale, skip=None):
+    def sgd_momentum(self, w, m, g, wb, lr_t, momentum, wd, grad_scale, skip=None, ema=None, ema_decay_t=None):
         """Fused SGD-momentum; skip = optional device int32 word: the launch changes nothing when
-        it holds a non-zero value at run time (a failed P2P gradient exchange)."""
+        it holds a non-zero value at run time (a failed P2P gradient exchange). ema (fp32, w's
+        length) with ema_decay_t (device fp32 scalar d): the same launch also applies
+        ema <- ema - (1 - d) * (ema - w_new) (the EMA kernel variant; skipped with the update)."""
         assert g.dtype in (torch.float32, torch.bfloat16) and g.numel() == w.numel()
+        if ema is not None:
+            assert ema_decay_t is not None and ema.dtype == ema_decay_t.dtype == torch.float32
+            assert ema.numel() == w.numel() and ema.data_ptr() % 16 == 0
+            _lib.check(self.L.drn_sgd_momentum_ema(w.data_ptr(), m.data_ptr(), g.data_ptr(),
+                                                   int(g.dtype == torch.bfloat16), _ptr(wb), w.numel(),
+                                                   lr_t.data_ptr(), float(momentum), float(wd), float(grad_scale),
+                                                   _ptr(skip), ema.data_ptr(), ema_decay_t.data_ptr(),
+                                                   self.stream()), "drn_sgd_momentum_ema")
+            return
         _lib.check(self.L.drn_sgd_momentum(w.data_ptr(), m.data_ptr(), g.data_ptr(), int(g.dtype == torch.bfloat16),
                                            _ptr(wb), w.numel(), lr_t.data_ptr(), float(momentum), float(wd),
                                            float(grad_scale), _ptr(skip), self.stream()), "drn_sgd_momentum")
 
     def lars_momentum(self, w, m, g, wb, table: LarsTable, first_slot, nslots, partials, trust, lr_t, momentum, wd,
-                      grad_scale, eta, eps, skip=None):
+                      grad_scale, eta, eps, skip=None, ema=None, ema_decay_t=None):
         """Fused LARS + momentum (sgd.hip) on slots [first_slot, first_slot + nslots) of `table`.
         w, m, g, wb are the whole flat buffers the table's offsets index; partials (2 fp32 per chunk
         of the table) and trust (1 fp32 per slot) are the caller's preallocated workspaces; trust
-        receives every updated slot's ratio. skip as in sgd_momentum (then trust is left alone too)."""
+        receives every updated slot's ratio. skip as in sgd_momentum (then trust is left alone too).
+        ema (a whole flat buffer like w) / ema_decay_t as in sgd_momentum: the update pass also
+        averages the updated slots' weights."""
         assert g.dtype in (torch.float32, torch.bfloat16) and g.numel() == w.numel() == m.numel()
         assert 0 <= first_slot and nslots >= 1 and first_slot + nslots <= table.n
         assert int(table.arr["offset"][table.n]) <= w.numel() and table.dev.device == w.device
@@ -951,6 +964,17 @@ class HipBackend(_Common):
             if self.L.drn_lars_slot_size() != LARS_SLOT.itemsize or self.L.drn_lars_chunk() != LARS_CHUNK:
                 raise _lib.KernelLibraryError("LarsSlot layout mismatch between Python and the kernel library")
             self._lars_checked = True
+        if ema is not None:
+            assert ema_decay_t is not None and ema.dtype == ema_decay_t.dtype == torch.float32
+            assert ema.numel() == w.numel() and ema.data_ptr() % 16 == 0
+            _lib.check(self.L.drn_lars_momentum_ema(w.data_ptr(), m.data_ptr(), g.data_ptr(),
+                                                    int(g.dtype == torch.bfloat16), _ptr(wb), table.dev.data_ptr(),
+                                                    int(first_slot), int(nslots), partials.data_ptr(),
+                                                    trust.data_ptr(), lr_t.data_ptr(), float(momentum), float(wd),
+                                                    float(grad_scale), float(eta), float(eps), _ptr(skip),
+                                                    ema.data_ptr(), ema_decay_t.data_ptr(), self.stream()),
+                       "drn_lars_momentum_ema")
+            return
         _lib.check(self.L.drn_lars_momentum(w.data_ptr(), m.data_ptr(), g.data_ptr(), int(g.dtype == torch.bfloat16),
                                             _ptr(wb), table.dev.data_ptr(), int(first_slot), int(nslots),
                                             partials.data_ptr(), trust.data_ptr(), lr_t.data_ptr(), float(momentum),
@@ -1313,7 +1337,12 @@ class RefBackend(_Common):
                 acc[:, r:r + (P - 1) * stride + 1:stride, s:s + (Q - 1) * stride + 1:stride, :] += m
         dx.copy_(acc[:, pad_h:pad_h + H, pad_w:pad_w + W, :])
 
-    def sgd_momentum(self, w, m, g, wb, lr_t, momentum, wd, grad_scale, skip=None):
+    @staticmethod
+    def _ema(ema, w, ema_decay_t):
+        """ema <- ema - (1 - d) * (ema - w), in the dtype of w (tf.train.ExponentialMovingAverage)."""
+        ema.sub_((ema - w) * (1.0 - float(ema_decay_t.reshape(-1)[0])))
+
+    def sgd_momentum(self, w, m, g, wb, lr_t, momentum, wd, grad_scale, skip=None, ema=None, ema_decay_t=None):
         if skip is not None and int(skip.reshape(-1)[0]) != 0:
             return
         lr = float(lr_t.reshape(-1)[0])
@@ -1322,9 +1351,11 @@ class RefBackend(_Common):
         w.sub_(lr * m)
         if wb is not None and wb.data_ptr() != w.data_ptr():
             wb.copy_(w)
+        if ema is not None:
+            self._ema(ema, w, ema_decay_t)
 
     def lars_momentum(self, w, m, g, wb, table: LarsTable, first_slot, nslots, partials, trust, lr_t, momentum, wd,
-                      grad_scale, eta, eps, skip=None):
+                      grad_scale, eta, eps, skip=None, ema=None, ema_decay_t=None):
         """HipBackend.lars_momentum's contract in torch, in the dtype of w (the oracle: fp64 under
         RefBackend(dtype=torch.float64)). partials is not used."""
         if skip is not None and int(skip.reshape(-1)[0]) != 0:
@@ -1347,6 +1378,8 @@ class RefBackend(_Common):
             ws.sub_(lr * ms)
             if wb is not None and wb.data_ptr() != w.data_ptr():
                 wb[sl].copy_(ws)
+            if ema is not None:
+                self._ema(ema[sl], ws, ema_decay_t)
             trust[i] = t
 
     def cast_bf16(self, x, y):

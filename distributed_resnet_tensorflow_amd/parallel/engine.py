@@ -321,6 +321,7 @@ class DataParallelEngine:
         weights and the refresh of the data-gradient weights."""
         if not self.zero1:
             # P2P: the optimizer reads the exchange's error word and skips a failed step's update
+            # (and, in the same kernel, the weight EMA's)
             self.ex.apply_gradients(grad_scale=grad_scale, grad=grad,
                                     skip=self.p2p.err if self.p2p is not None else None)
             return
@@ -338,11 +339,12 @@ class DataParallelEngine:
         self.ex.refresh_dgrad_weights()
 
     def gather_state(self):
-        """ZeRO-1: make the fp32 masters and momentum complete on every rank (collective; before a
-        checkpoint or anything else that reads them). No-op otherwise."""
+        """ZeRO-1: make the fp32 masters, momentum and weight EMA (each rank averages its shards
+        only) complete on every rank (collective; before a checkpoint or anything else that reads
+        them). No-op otherwise."""
         if not self.zero1:
             return
-        for t in (self.P.master, self.P.momentum):
+        for t in (self.P.master, self.P.momentum) + ((self.P.ema,) if self.P.ema is not None else ()):
             for lo, hi in self.buckets:
                 if self._sharded(lo, hi):
                     s0, s1 = self._shard(lo, hi)
@@ -412,7 +414,7 @@ class DataParallelEngine:
     # -- state sync -----------------------------------------------------------------------------------
     def broadcast_parameters(self, src: int = 0):
         """Rank-0 broadcast of every variable (Horovod BroadcastGlobalVariablesHook(0) analog)."""
-        for t in (self.P.master, self.P.momentum, self.P.bn_state):
+        for t in (self.P.master, self.P.momentum, self.P.bn_state) + ((self.P.ema,) if self.P.ema is not None else ()):
             dist.broadcast(t, src=src, group=self.group)
         step = torch.tensor([self.P.global_step], dtype=torch.int64,
                             device=self.P.master.device)

@@ -22,6 +22,7 @@ start bucket all-reduces while earlier layers are still back-propagating.
 """
 from __future__ import annotations
 
+import contextlib
 import os
 
 from dataclasses import dataclass
@@ -104,7 +105,8 @@ class Executor:
     def __init__(self, spec: NetSpec, batch: int, backend, device, seed: int = 0,
                  weight_decay: float = 2e-4, momentum: float = 0.9, params: ParamStore | None = None,
                  materialize_bn: Optional[bool] = None, optimizer: str = "momentum", lars_eta: float = 0.001,
-                 lars_eps: float = 1e-9, label_smoothing: float = 0.0, top_k: int = 0):
+                 lars_eps: float = 1e-9, label_smoothing: float = 0.0, top_k: int = 0, ema_decay: float = 0.0,
+                 ema_warmup: bool = True):
         self.spec, self.N, self.be = spec, batch, backend
         # "momentum": the reference's MomentumOptimizer; "lars": the same update with each conv /
         # dense kernel's gradient (weight decay included) scaled by its layer-wise trust ratio
@@ -121,6 +123,13 @@ class Executor:
         if int(top_k) != top_k or top_k < 0:
             raise ValueError(f"top_k must be an integer >= 0, got {top_k!r}")
         self.label_smoothing, self.top_k = float(label_smoothing), int(top_k)
+        # ema_decay > 0: an exponential moving average of every trainable variable (P.ema; TF's
+        # ExponentialMovingAverage shadow variables), updated by the optimizer's own kernels after
+        # each update (csrc/kernels/sgd.hip *_ema_kernel). ema_warmup: TF's num_updates form, the
+        # decay of update t is min(ema_decay, (1 + t) / (10 + t)). 0: no buffer, the plain kernels
+        if not 0.0 <= ema_decay < 1.0:
+            raise ValueError(f"ema_decay must be in [0, 1), got {ema_decay!r}")
+        self.ema_decay, self.ema_warmup = float(ema_decay), bool(ema_warmup)
         # fuse each BN's backward reduction into the epilogue of the data-gradient conv feeding it
         self.fuse_bn_bwd = True
         # (The BN backward applied on load by both 1x1 consumers instead of materialised -- the
@@ -227,7 +236,10 @@ class Executor:
         self.early_sgd = os.environ.get("DRN_EARLY_SGD", "1") == "1"
         self._pre_ev, self._pre_lo = None, 0
         self.fdt = backend.acc_dtype
-        self.P = params or ParamStore(spec, self.device, keep_bf16=self.is_hip, seed=seed, dtype=self.fdt)
+        self.P = params or ParamStore(spec, self.device, keep_bf16=self.is_hip, seed=seed, dtype=self.fdt,
+                                      ema=self.ema_decay > 0)
+        if self.ema_decay > 0:
+            self.P.enable_ema()   # (a store handed in without the buffer)
         self.grad_ready: Optional[Callable[[int], None]] = None
         self._alloc()
         self.sync_weights()
@@ -524,6 +536,12 @@ class Executor:
                     n *= d
                 ph.wt = self.wt_flat[ph.wt_off:ph.wt_off + n].view(ph.wt_shape)
         self.lr_t = self._f32(1)
+        # the EMA decay of the coming update: device memory like the LR (set_ema_decay), so graph
+        # and plan replays read the value of their step, not the one of the capture
+        self.ema_decay_t = None
+        if self.ema_decay > 0:
+            self.ema_decay_t = torch.zeros(1, dtype=torch.float32, device=self.device)
+            self.set_ema_decay(self.P.global_step)
         # LARS: the slot table, the norms workspace and the per-slot trust ratios, allocated once
         # (a captured graph / recorded plan replays with these pointers)
         self.lars_table = self.lars_partials = self.lars_trust = None
@@ -554,6 +572,23 @@ class Executor:
             else:
                 self.be.weight_tflip(src, self.wt_flat, self.wt_table.cpu(), self.wt_n, self.wt_total)
         self._repack_stem()
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Within the block the network runs on the averaged weights (P.ema) -- for an evaluation
+        forward; on exit the trained weights and their compute copies are back, bit for bit. Not
+        for training steps: an update inside the block would be lost."""
+        P = self.P
+        if P.ema is None:
+            raise RuntimeError("no weight EMA is kept (Executor(ema_decay=0))")
+        saved = P.master.clone()
+        P.master.copy_(P.ema)
+        self.sync_weights()
+        try:
+            yield self
+        finally:
+            P.master.copy_(saved)
+            self.sync_weights()
 
     def _repack_stem(self):
         """Packed stem weights [K][7][8][4] from the bf16 compute copy (after every update)."""
@@ -958,6 +993,18 @@ class Executor:
     def set_lr(self, lr: float):
         self.be.fill_(self.lr_t, float(lr))
 
+    def ema_decay_at(self, step: int) -> float:
+        """The decay d_t of the update that follows `step` completed updates."""
+        if self.ema_warmup:
+            return min(self.ema_decay, (1.0 + step) / (10.0 + step))
+        return self.ema_decay
+
+    def set_ema_decay(self, step: int):
+        """Write the coming update's EMA decay (wherever the LR is written per step). No-op with the
+        EMA off."""
+        if self.ema_decay_t is not None:
+            self.be.fill_(self.ema_decay_t, self.ema_decay_at(int(step)))
+
     def join_grads(self):
         """Make the current stream wait for a stem weight gradient deferred by backward() (its
         event only: work queued on the side stream after it -- the data-gradient weight refresh
@@ -973,13 +1020,27 @@ class Executor:
         P = self.P
         if self.optimizer == "lars":
             first, n = self.lars_table.slot_range(lo, hi)
-            self.be.lars_momentum(P.master, P.momentum, g, P.wbf16, self.lars_table, first, n, self.lars_partials,
-                                  self.lars_trust, self.lr_t, self.mom, self.wd, grad_scale, self.lars_eta,
-                                  self.lars_eps, skip)
+            if P.ema is None:
+                self.be.lars_momentum(P.master, P.momentum, g, P.wbf16, self.lars_table, first, n,
+                                      self.lars_partials, self.lars_trust, self.lr_t, self.mom, self.wd, grad_scale,
+                                      self.lars_eta, self.lars_eps, skip)
+            else:
+                self.be.lars_momentum(P.master, P.momentum, g, P.wbf16, self.lars_table, first, n,
+                                      self.lars_partials, self.lars_trust, self.lr_t, self.mom, self.wd, grad_scale,
+                                      self.lars_eta, self.lars_eps, skip, ema=P.ema, ema_decay_t=self.ema_decay_t)
             return
+        self._sgd(lo, hi, g, grad_scale, skip)
+
+    def _sgd(self, lo: int, hi: int, g: torch.Tensor, grad_scale: float, skip=None):
+        """SGD-momentum on the flat range [lo, hi) (+ its slice of the EMA when that is kept)."""
+        P = self.P
         wb = P.wbf16[lo:hi] if P.wbf16 is not None else None
-        self.be.sgd_momentum(P.master[lo:hi], P.momentum[lo:hi], g[lo:hi], wb, self.lr_t, self.mom, self.wd,
-                             grad_scale, skip)
+        if P.ema is None:
+            self.be.sgd_momentum(P.master[lo:hi], P.momentum[lo:hi], g[lo:hi], wb, self.lr_t, self.mom, self.wd,
+                                 grad_scale, skip)
+        else:
+            self.be.sgd_momentum(P.master[lo:hi], P.momentum[lo:hi], g[lo:hi], wb, self.lr_t, self.mom, self.wd,
+                                 grad_scale, skip, ema=P.ema[lo:hi], ema_decay_t=self.ema_decay_t)
 
     def apply_gradients(self, grad_scale: float = 1.0, grad: Optional[torch.Tensor] = None,
                         skip: Optional[torch.Tensor] = None):
@@ -1017,11 +1078,7 @@ class Executor:
         if self.optimizer == "lars":
             raise RuntimeError("the sharded optimizer cuts tensors across ranks; LARS needs every tensor's whole "
                                "norm (optimizer='lars' does not support optimizer sharding)")
-        P = self.P
-        g = P.grad if grad is None else grad
-        wb = P.wbf16[lo:hi] if P.wbf16 is not None else None
-        self.be.sgd_momentum(P.master[lo:hi], P.momentum[lo:hi], g[lo:hi], wb, self.lr_t, self.mom, self.wd,
-                             grad_scale)
+        self._sgd(lo, hi, self.P.grad if grad is None else grad, grad_scale)
 
     def refresh_dgrad_weights(self, stem: bool = True):
         """Rebuild the flipped / channel-transposed data-gradient weights (and the packed stem's
@@ -1113,6 +1170,7 @@ class Executor:
     def train_step(self, lr: Optional[float] = None, grad_scale: float = 1.0, allreduce: Optional[Callable] = None):
         if lr is not None:
             self.set_lr(lr)
+        self.set_ema_decay(self.P.global_step)
         self.forward(train=True)
         self.backward(defer_tail=allreduce is None and not self.check_nan)
         if self.check_nan:

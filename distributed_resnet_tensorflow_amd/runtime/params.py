@@ -55,7 +55,8 @@ def _trunc_normal(shape, std, gen):
 
 
 class ParamStore:
-    def __init__(self, spec: NetSpec, device, keep_bf16: bool, seed: int = 0, dtype=torch.float32):
+    def __init__(self, spec: NetSpec, device, keep_bf16: bool, seed: int = 0, dtype=torch.float32,
+                 ema: bool = False):
         self.spec = spec
         self.device = torch.device(device)
         self.slots: list[Slot] = []
@@ -80,6 +81,9 @@ class ParamStore:
         self.momentum = torch.zeros(self.total, **f32)
         self.grad = torch.zeros(self.total, **f32)
         self.wbf16 = torch.zeros(self.total, dtype=torch.bfloat16, device=self.device) if keep_bf16 else None
+        # exponential moving average of the trainable variables (tf.train.ExponentialMovingAverage's
+        # shadow variables) in the master's layout; allocated only when the average is kept
+        self.ema = torch.zeros(self.total, **f32) if ema else None
         # BN moving statistics (non-trainable), one flat buffer: [mean | var] per BN
         self.bn_slots = {}
         boff = 0
@@ -128,6 +132,7 @@ class ParamStore:
                 lim = math.sqrt(6.0 / (fan_in + fan_out))
                 v.copy_(torch.rand(s.shape, generator=gen) * 2 * lim - lim)
         self.master.copy_(host)
+        self.seed_ema()
         self.momentum.zero_()
         self.grad.zero_()
         bs = torch.zeros_like(self.bn_state, device="cpu")
@@ -135,6 +140,20 @@ class ParamStore:
             bs[off + _round(c):off + _round(c) + c] = 1.0
         self.bn_state.copy_(bs)
         self.global_step = 0
+
+    def enable_ema(self):
+        """Allocate the EMA buffer (once), starting equal to the variables."""
+        if self.ema is None:
+            self.ema = self.master.clone()
+
+    def seed_ema(self, name: str | None = None):
+        """Shadow values start equal to the variables: all of them, or variable `name` only."""
+        if self.ema is None:
+            return
+        if name is None:
+            self.ema.copy_(self.master)
+        else:
+            self.view(self.ema, name).copy_(self.view(self.master, name))
 
     # -- TF-layout export / import (checkpoint) ----------------------------------------------
     def to_tf(self, name: str, buf: torch.Tensor | None = None, dtype=torch.float32) -> torch.Tensor:

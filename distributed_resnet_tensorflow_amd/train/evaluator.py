@@ -5,6 +5,8 @@ resnet_imagenet_eval.py:154-210): restore the latest checkpoint in --log_root, r
 checkpoint's global step, sleep and repeat unless --eval_once. With --top_k=K (K >= 2) the top-K
 precision is accumulated beside it (`precision@K` in the log, `Precision@K` / `Best Precision@K`
 summaries, `precision_top_k` in the results and in best_precision.json); "best" stays top-1.
+With --eval_ema the checkpoint's `<var>/ExponentialMovingAverage` tensors (training with
+--ema_decay) are evaluated in place of the variables; best_precision.json then records "ema": true.
 
 Fixes of reference quirks: no busy-spin when there is no checkpoint (Q8), best precision
 persisted in eval_dir/best_precision.json across restarts (Q11), the eval set is read in order
@@ -22,7 +24,7 @@ import torch
 from ..ckpt.saver import Saver, latest_checkpoint, step_of
 from ..parallel import cluster as cl
 from ..runtime.executor import Executor
-from ..runtime.state import import_state
+from ..runtime.state import NoEmaInCheckpoint, has_ema, import_state
 from ..utils.events import EventFileWriter
 from .session import make_backend
 from .trainer import WEIGHT_DECAY, apply_thread_flags, make_feeder, model_spec_from_flags, setup_logging
@@ -55,6 +57,7 @@ def evaluate(FLAGS, eval_batch_size: int = 100, max_evals: int = -1):
     best_path = os.path.join(FLAGS.eval_dir, "best_precision.json") if FLAGS.eval_dir else None
     best = _load_best(best_path) if best_path else 0.0
     best_k = _load_best(best_path, "best_precision_top_k") if best_path and top_k else 0.0
+    eval_ema = bool(getattr(FLAGS, "eval_ema", False))
     last = None
     n_eval = 0
     results = []
@@ -66,7 +69,12 @@ def evaluate(FLAGS, eval_batch_size: int = 100, max_evals: int = -1):
             pass
         else:
             try:
-                import_state(ex, Saver.restore(prefix))
+                tensors = Saver.restore(prefix)
+                if eval_ema and not has_ema(tensors):
+                    # (not a half-written checkpoint: waiting for the next one does not help)
+                    raise NoEmaInCheckpoint(f"--eval_ema: checkpoint {prefix} has no ExponentialMovingAverage "
+                                            "tensors (train with --ema_decay > 0)")
+                import_state(ex, tensors, use_ema=eval_ema)
             except (OSError, ValueError, KeyError) as e:  # half-written / rotated away: retry later
                 log.warning("Cannot restore checkpoint %s: %s", prefix, e)
                 prefix = None
@@ -94,6 +102,8 @@ def evaluate(FLAGS, eval_batch_size: int = 100, max_evals: int = -1):
                 best = max(best, precision)
                 scalars = {"Precision": precision, "Best Precision": best}
                 record = {"best_precision": best, "step": step}
+                if eval_ema:
+                    record["ema"] = True
                 result = {"step": step, "loss": loss, "precision": precision, "best_precision": best}
                 line = "loss: %.3f, precision: %.3f, best precision: %.3f" % (loss, precision, best)
                 if top_k:

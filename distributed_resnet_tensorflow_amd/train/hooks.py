@@ -99,6 +99,8 @@ class SummaryHook(Hook):
                    "learning_rate": m["learning_rate"], "Precision": m["precision"]}
         if "precision_top_k" in m:
             scalars[f"Precision@{_top_k(sess)}"] = m["precision_top_k"]
+        if "ema_decay" in m:  # (--ema_decay > 0: the last update's effective decay, warm-up included)
+            scalars["ema/decay"] = m["ema_decay"]
         ex = getattr(sess, "ex", None)
         if getattr(ex, "optimizer", "momentum") == "lars":
             # the last update's trust ratios of the adapting (conv / dense kernel) slots

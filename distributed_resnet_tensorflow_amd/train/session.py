@@ -79,14 +79,16 @@ class TrainingSession:
                  bucket_mb: float = 25.0, meta: Optional[dict] = None, allreduce: str = "rccl", wire: str = "fp32",
                  collective_timeout_s: float = 0.0, precision: str = "bf16", shard_optimizer: bool = False,
                  step_trial: bool = True, optimizer: str = "momentum", lars_eta: float = 0.001,
-                 lars_eps: float = 1e-9, label_smoothing: float = 0.0, top_k: int = 0):
+                 lars_eps: float = 1e-9, label_smoothing: float = 0.0, top_k: int = 0, ema_decay: float = 0.0,
+                 ema_warmup: bool = True):
         self.cluster = cluster
         self.spec = spec
         self.device = torch.device(cluster.device)
         self.be = make_backend(cluster.device, precision)
         self.ex = Executor(spec, batch, self.be, self.device, seed=seed, weight_decay=weight_decay,
                            optimizer=optimizer, lars_eta=lars_eta, lars_eps=lars_eps,
-                           label_smoothing=label_smoothing, top_k=top_k)
+                           label_smoothing=label_smoothing, top_k=top_k, ema_decay=ema_decay,
+                           ema_warmup=ema_warmup)
         self.lr = lr_schedule
         self.meta = meta or {}
         # DRN_FORCE_DP=1: the data-parallel engine on a single-rank process group (profiling the
@@ -185,6 +187,7 @@ class TrainingSession:
         self._graph: Optional[StepGraph] = None
         self._metrics_cache = None
         self.cur_lr = float("nan")
+        self.cur_ema_decay = float("nan")
         # set when a step's gradient exchange failed: no further checkpoint may be written
         self.failed: Optional[str] = None
         if os.environ.get("DRN_ROCTX") == "1":
@@ -206,6 +209,9 @@ class TrainingSession:
             if was != self.ex.label_smoothing:
                 log.warning("checkpoint was trained with label_smoothing %g, continuing with %g", was,
                             self.ex.label_smoothing)
+            was = Saver.restore_meta(prefix)["ema_decay"]
+            if was != self.ex.ema_decay:
+                log.warning("checkpoint was trained with ema_decay %g, continuing with %g", was, self.ex.ema_decay)
         if self.engine is not None:
             self.engine.broadcast_parameters()
             if self.cluster.is_chief is False:
@@ -275,6 +281,9 @@ class TrainingSession:
         """One synchronous training step on the batch already in ex.images / ex.labels."""
         self.cur_lr = self.lr.lr_for_step()
         self.ex.set_lr(self.cur_lr)
+        # (device memory like the LR: graph and plan replays read this step's warm-up value)
+        self.ex.set_ema_decay(self.ex.P.global_step)
+        self.cur_ema_decay = self.ex.ema_decay_at(self.ex.P.global_step)
         if self.use_graph and not self.ex.check_nan:  # the debug checks synchronize: no capture
             if self._graph is None:  # warm-up = this real step
                 if self.engine is not None and self.engine.p2p is None:
@@ -455,6 +464,8 @@ class TrainingSession:
         if self._metrics_cache is None:
             m = self.ex.metrics()
             m["learning_rate"] = self.cur_lr
+            if self.ex.ema_decay > 0:
+                m["ema_decay"] = self.cur_ema_decay   # the effective d_t of the last update
             if self.engine is not None:
                 m.update(self.engine.stats())
                 self._guard(self.engine.check_errors)

@@ -54,7 +54,7 @@ def _meta(FLAGS, spec):
             "num_classes": spec.num_classes,
             "spec_name": spec.name,
             "optimizer": FLAGS.optimizer, "eta": FLAGS.lars_eta, "eps": FLAGS.lars_eps,
-            "label_smoothing": FLAGS.label_smoothing}
+            "label_smoothing": FLAGS.label_smoothing, "ema_decay": FLAGS.ema_decay}
 
 
 def make_feeder(FLAGS, ex, cluster, is_training: bool, data_state=None, batch=None):
@@ -111,7 +111,8 @@ def train(FLAGS, cluster=None):
                            collective_timeout_s=FLAGS.collective_timeout_secs, precision=FLAGS.precision,
                            shard_optimizer=FLAGS.optimizer_sharding, optimizer=FLAGS.optimizer,
                            lars_eta=FLAGS.lars_eta, lars_eps=FLAGS.lars_eps,
-                           label_smoothing=FLAGS.label_smoothing, top_k=FLAGS.top_k)
+                           label_smoothing=FLAGS.label_smoothing, top_k=FLAGS.top_k, ema_decay=FLAGS.ema_decay,
+                           ema_warmup=FLAGS.ema_warmup)
     feeder = make_feeder(FLAGS, sess.ex, cluster, True, sess.data_state)
     is_imagenet = FLAGS.dataset == "imagenet"
     hooks = [LoggingHook(FLAGS.log_every_n_steps, FLAGS.batch_size * cluster.world,
