@@ -1,6 +1,7 @@
 // head.hip — classifier head on gfx950: final BN-ReLU + global average pool, dense layer
 // (fp32 GEMMs), softmax cross-entropy with one-hot labels and the batch precision metric, and its
-// label-smoothing / top-k variant (softmax_xent_ex_kernel).
+// label-smoothing / top-k variant (softmax_xent_ex_kernel), and that against the two-label target of
+// Mixup / CutMix (softmax_xent_mix_kernel).
 //
 // Reference: final batch_norm_relu + average_pooling2d(VALID, pool = H) + dense
 // (resnet_model_official.py:268-275 CIFAR, :336-343 ImageNet); softmax + mean
@@ -314,6 +315,131 @@ __global__ __launch_bounds__(256) void softmax_xent_ex_kernel(const float* __res
   }
 }
 
+// softmax_xent_ex_kernel against a target mixed from two labels (Mixup / CutMix): sample n's second
+// label yb and weight lam come from its record of the batch's mix table (csrc/kernels/mix.hip
+// MixRec), read from device memory when the kernel runs, so a graph or plan replay follows the
+// table of its batch:
+//   t_j     = (1 - eps) (lam [j == ya] + (1 - lam) [j == yb]) + eps / K
+//   loss    = log(se) - (1 - eps) (lam (z_ya - mx) + (1 - lam) (z_yb - mx)) - (eps / K) sum_j (z_j - mx)
+//   dlogits = (p_j - t_j) * grad_scale
+// correct / correct_k: the rank rule against the dominant label (ya if lam >= 0.5, else yb).
+// A separate kernel, not a flag of softmax_xent_ex_kernel: that one's code stays as it is. The
+// reductions are its reductions in its order, and a record with lam == 1 takes its expressions (yb
+// is then not read at all, whatever its value), so with lam == 1 everywhere every output is its
+// bits. A yb outside [0, ncls) with lam != 1 reads nothing either: NaN loss, like a bad label.
+struct XentMixRec {  // mix.hip MixRec
+  float w, lam;
+  int32_t y0, x0, y1, x1;
+  int32_t label_b, pad_;
+};
+static_assert(sizeof(XentMixRec) == 32, "the 32-byte mix record");
+
+template <bool REG>
+__global__ __launch_bounds__(256) void softmax_xent_mix_kernel(const float* __restrict__ logits,
+                                                               const int* __restrict__ labels,
+                                                               const XentMixRec* __restrict__ table, int ncls,
+                                                               float grad_scale, float smoothing, int top_k,
+                                                               float* __restrict__ dlogits, float* __restrict__ loss,
+                                                               float* __restrict__ probs, int* __restrict__ correct,
+                                                               int* __restrict__ correct_k) {
+  const int n = blockIdx.x;
+  const float* z = logits + (size_t)n * ncls;
+  __shared__ float sred[8], ssum[8];
+  __shared__ int sidx[8], scnt[8];
+  const int ya = labels[n];
+  const float lam = table[n].lam;
+  const bool pure = lam == 1.f;
+  const int yb = pure ? -1 : table[n].label_b;
+  const bool aok = (unsigned)ya < (unsigned)ncls, bok = (unsigned)yb < (unsigned)ncls;
+  const float zya = aok ? z[ya] : __builtin_nanf("");
+  const float zyb = bok ? z[yb] : __builtin_nanf("");
+  // the dominant label: what correct / correct_k are counted against
+  const bool dom_a = lam >= 0.5f;
+  const int y = dom_a ? ya : yb;
+  const float zy = dom_a ? zya : zyb;
+  const int iters = REG ? XENT_REG_ROW : (ncls + 255) / 256;
+  float r[XENT_REG_ROW];
+  if (REG) {
+#pragma unroll
+    for (int i = 0; i < XENT_REG_ROW; ++i) {
+      const int j = threadIdx.x + 256 * i;
+      r[i] = j < ncls ? z[j] : -INFINITY;
+    }
+  }
+  auto at = [&](int i, int j) { return REG ? r[i] : z[j]; };
+  float mx = -INFINITY;
+  int amax = 0, cnt = 0;
+#pragma unroll
+  for (int i = 0; i < iters; ++i) {
+    const int j = threadIdx.x + 256 * i;
+    if (j < ncls) {
+      const float v = at(i, j);
+      if (v > mx) { mx = v; amax = j; }
+      cnt += (v > zy || (v == zy && j < y)) ? 1 : 0;
+    }
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(mx, o, 64);
+    const int oi = __shfl_xor(amax, o, 64);
+    if (ov > mx || (ov == mx && oi < amax)) { mx = ov; amax = oi; }
+    cnt += __shfl_xor(cnt, o, 64);
+  }
+  const int w = threadIdx.x >> 6, l = threadIdx.x & 63, nw = blockDim.x >> 6;
+  if (l == 0) { sred[w] = mx; sidx[w] = amax; scnt[w] = cnt; }
+  __syncthreads();
+  mx = sred[0]; amax = sidx[0]; cnt = scnt[0];
+  for (int i = 1; i < nw; ++i) {
+    if (sred[i] > mx || (sred[i] == mx && sidx[i] < amax)) { mx = sred[i]; amax = sidx[i]; }
+    cnt += scnt[i];
+  }
+  __syncthreads();
+  float se = 0.f, sz = 0.f;
+#pragma unroll
+  for (int i = 0; i < iters; ++i) {
+    const int j = threadIdx.x + 256 * i;
+    if (j < ncls) {
+      const float d = at(i, j) - mx;
+      se += __expf(d);
+      sz += d;
+    }
+  }
+  se = wave_sum(se);
+  sz = wave_sum(sz);
+  if (l == 0) { sred[w] = se; ssum[w] = sz; }
+  __syncthreads();
+  se = 0.f; sz = 0.f;
+  for (int i = 0; i < nw; ++i) { se += sred[i]; sz += ssum[i]; }
+  const float inv = 1.f / se;
+  const float uni = smoothing / (float)ncls, hot = 1.f - smoothing;
+  // the two hot entries of the target; lam == 1: (hot, nothing), softmax_xent_ex_kernel's row
+  const float ha = pure ? hot : hot * lam, hb = hot * (1.f - lam);
+#pragma unroll
+  for (int i = 0; i < iters; ++i) {
+    const int j = threadIdx.x + 256 * i;
+    if (j < ncls) {
+      const float p = __expf(at(i, j) - mx) * inv;
+      if (probs) probs[(size_t)n * ncls + j] = p;
+      if (dlogits) {
+        float t = j == ya ? ha : 0.f;
+        if (j == yb) t += hb;
+        dlogits[(size_t)n * ncls + j] = (p - t - uni) * grad_scale;
+      }
+    }
+  }
+  if (threadIdx.x == 0) {
+    float ls;
+    if (pure) {
+      ls = smoothing == 0.f ? (mx + __logf(se)) - zya : __logf(se) - hot * (zya - mx) - uni * sz;
+    } else {
+      const float mz = lam * (zya - mx) + (1.f - lam) * (zyb - mx);
+      ls = smoothing == 0.f ? __logf(se) - mz : __logf(se) - hot * mz - uni * sz;
+    }
+    loss[n] = ls;
+    if (correct) correct[n] = (amax == y) ? 1 : 0;
+    if (correct_k) correct_k[n] = (zy == zy && cnt < top_k) ? 1 : 0;
+  }
+}
+
 // column sums: out[j] = scale * sum_n in[n][j]  (dense bias gradient)
 // Column sums (the dense bias gradient, sum over the batch of dlogits): a block covers 32
 // columns with 8 row slices of 32 lanes (coalesced 128-byte row segments, 4 independent loads
@@ -385,6 +511,19 @@ DRN_API int drn_softmax_xent_ex(const float* logits, const int* labels, int N, i
   auto kern = ncls <= 256 * drn::XENT_REG_ROW ? drn::softmax_xent_ex_kernel<true> : drn::softmax_xent_ex_kernel<false>;
   drn::launch(kern, dim3(N), dim3(256), 0, s, logits, labels, ncls, grad_scale, smoothing, top_k, dlogits, loss,
                      probs, correct, correct_k);
+  return (int)hipGetLastError();
+}
+
+// drn_softmax_xent_ex against the two-label target of a mix table (N 32-byte records in device
+// memory, csrc/kernels/mix.hip): one launch, one workgroup per sample.
+DRN_API int drn_softmax_xent_mix(const float* logits, const int* labels, const void* table, int N, int ncls,
+                                 float grad_scale, float smoothing, int top_k, float* dlogits, float* loss,
+                                 float* probs, int* correct, int* correct_k, hipStream_t s) {
+  if (!(smoothing >= 0.f && smoothing < 1.f) || top_k < 1 || N < 1 || ncls < 1 || table == nullptr)
+    return (int)hipErrorInvalidValue;
+  auto kern = ncls <= 256 * drn::XENT_REG_ROW ? drn::softmax_xent_mix_kernel<true> : drn::softmax_xent_mix_kernel<false>;
+  drn::launch(kern, dim3(N), dim3(256), 0, s, logits, labels, (const drn::XentMixRec*)table, ncls, grad_scale,
+                     smoothing, top_k, dlogits, loss, probs, correct, correct_k);
   return (int)hipGetLastError();
 }
 

@@ -168,8 +168,8 @@ class Saver:
     @staticmethod
     def restore_meta(prefix: str) -> dict:
         """The checkpoint's `.meta` model description with the keys later versions added filled in
-        (label_smoothing: 0 and ema_decay: 0, what every checkpoint without the key was trained
-        with); {} plus those defaults when the file is missing or unreadable."""
+        (label_smoothing, ema_decay, mixup_alpha and cutmix_alpha: 0, what every checkpoint without
+        the key was trained with); {} plus those defaults when the file is missing or unreadable."""
         try:
             with open(prefix + ".meta") as f:
                 meta = dict(json.load(f))
@@ -177,4 +177,6 @@ class Saver:
             meta = {}
         meta["label_smoothing"] = float(meta.get("label_smoothing", 0.0))
         meta["ema_decay"] = float(meta.get("ema_decay", 0.0))
+        meta["mixup_alpha"] = float(meta.get("mixup_alpha", 0.0))
+        meta["cutmix_alpha"] = float(meta.get("cutmix_alpha", 0.0))
         return meta

@@ -167,6 +167,15 @@ def validate(fv: "FlagValues") -> None:
         raise FlagsError(f"--ema_decay must be in [0, 1), got {fv.ema_decay!r}")
     if fv.ema_decay > 0 and fv.model == "lrnet":
         raise FlagsError("--ema_decay is not supported by --model=lrnet (its Adam path keeps no weight average)")
+    if fv.mixup_alpha < 0 or fv.cutmix_alpha < 0:
+        raise FlagsError(f"--mixup_alpha and --cutmix_alpha must be >= 0, got {fv.mixup_alpha!r}, "
+                         f"{fv.cutmix_alpha!r}")
+    if not 0.0 <= fv.mix_prob <= 1.0:
+        raise FlagsError(f"--mix_prob must be in [0, 1], got {fv.mix_prob!r}")
+    if not 0.0 <= fv.mix_switch_prob <= 1.0:
+        raise FlagsError(f"--mix_switch_prob must be in [0, 1], got {fv.mix_switch_prob!r}")
+    if (fv.mixup_alpha > 0 or fv.cutmix_alpha > 0) and fv.model == "lrnet":
+        raise FlagsError("--mixup_alpha / --cutmix_alpha are not supported by --model=lrnet")
 
 
 FLAGS = FlagValues()
@@ -273,6 +282,14 @@ def define_reference_flags(flag_values: FlagValues = FLAGS, **defaults) -> FlagV
       fv)
     B("eval_ema", False, "--mode=eval: evaluate the checkpoint's <var>/ExponentialMovingAverage tensors in place of "
       "the variables (an error if it was trained without --ema_decay).", fv)
+    Fl("mixup_alpha", 0.0, "a > 0: Mixup (Zhang et al. 2018): every training batch is blended with its own reversal, "
+       "lam ~ Beta(a, a), images and targets alike (HIP kernels; the logged precision then counts the dominant "
+       "label). 0 = off.", fv)
+    Fl("cutmix_alpha", 0.0, "a > 0: CutMix (Yun et al. 2019): a box of area 1 - lam0, lam0 ~ Beta(a, a), of every "
+       "training image is replaced by its partner's; the target weight is the area kept. 0 = off.", fv)
+    Fl("mix_prob", 1.0, "Probability that a training batch is mixed (--mixup_alpha / --cutmix_alpha).", fv)
+    Fl("mix_switch_prob", 0.5, "With both --mixup_alpha and --cutmix_alpha on: probability of CutMix.", fv)
+    B("mix_per_sample", False, "Draw the mix kind, lam and box per sample instead of once per batch.", fv)
     I("collective_timeout_secs", 600, "Process-group timeout and collective-watchdog limit: a rank whose "
       "gradient exchange stalls this long exits (the launcher restarts the job from its checkpoint).", fv)
     I("fault_inject_step", -1, "Kill this process at the given global step (fault-injection tests).", fv)

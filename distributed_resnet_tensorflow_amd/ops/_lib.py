@@ -120,6 +120,10 @@ _SIGS = {
                    c_p], c_int),
     "drn_softmax_xent": ([c_p, c_p, c_int, c_int, c_f, c_p, c_p, c_p, c_p, c_p], c_int),
     "drn_softmax_xent_ex": ([c_p, c_p, c_int, c_int, c_f, c_f, c_int, c_p, c_p, c_p, c_p, c_p, c_p], c_int),
+    # ... against the two-label Mixup / CutMix target: + the mix table (N 32-byte records) after the labels
+    "drn_softmax_xent_mix": ([c_p, c_p, c_p, c_int, c_int, c_f, c_f, c_int, c_p, c_p, c_p, c_p, c_p, c_p], c_int),
+    "drn_mix_pairs": ([c_p, c_p, c_p, c_int, c_int, c_int, c_p], c_int),
+    "drn_mix_rec_size": ([], c_int),
     "drn_colsum": ([c_p, c_int, c_int, c_p, c_f, c_int, c_p], c_int),
     "drn_maxpool_fwd": ([c_p, c_p, c_p] + [c_int] * 10 + [c_p, c_int, c_p], c_int),
     "drn_maxpool_bwd": ([c_p, c_p, c_p] + [c_int] * 10 + [c_p], c_int),

@@ -12,7 +12,8 @@ Op contract (NHWC activations, KRSC conv weights, fp32 statistics):
   conv_wgrad(x, dy, out, g, in_bn, relu_in, ws, splits)      out = dW (fp32, KRSC)
   bn_stats / bn_finalize / bn_inference / bn_apply
   bn_bwd_reduce / bn_finalize_bwd / bn_bwd_apply
-  pool_bnrelu, sgemm, softmax_xent(_ex), colsum, maxpool_fwd/bwd, sgd_momentum, weight_tflip
+  pool_bnrelu, sgemm, softmax_xent(_ex, _mix), colsum, maxpool_fwd/bwd, sgd_momentum, weight_tflip
+  mix_pairs(src, dst, table)                                 Mixup / CutMix of a batch with its reversal
 where pre(x) = relu(x * scale + shift) when in_bn = (scale, shift) is given.
 """
 from __future__ import annotations
@@ -120,6 +121,37 @@ def lars_table(store, device=None) -> LarsTable:
     from ..runtime.params import _round
     return LarsTable([(s.offset, s.numel, _round(s.numel), s.kind not in LARS_EXCLUDED) for s in store.slots],
                      store.device if device is None else device)
+
+
+# mirror of mix.hip `struct MixRec`: one record per sample of a Mixup / CutMix batch (partner of sample
+# n: N - 1 - n). Image: the partner's pixel inside the half-open box [y0, y1) x [x0, x1), elsewhere
+# w * own + (1 - w) * partner. Target: lam on the sample's own label, 1 - lam on label_b.
+MIX_REC = np.dtype([("w", "<f4"), ("lam", "<f4"), ("y0", "<i4"), ("x0", "<i4"), ("y1", "<i4"), ("x1", "<i4"),
+                    ("label_b", "<i4"), ("pad_", "<i4")])
+
+
+def mix_identity(n: int) -> np.ndarray:
+    """n identity records: nothing is mixed (w = lam = 1, empty box, label_b = 0)."""
+    t = np.zeros(n, dtype=MIX_REC)
+    t["w"] = t["lam"] = 1.0
+    return t
+
+
+def mix_table_tensor(table) -> torch.Tensor:
+    """A mix table (numpy MIX_REC [N], or already an int32 [N, 8] tensor) as the int32 [N, 8] tensor
+    both backends take: the records' bytes, columns 0 / 1 holding the bits of w / lam."""
+    if isinstance(table, torch.Tensor):
+        assert table.dtype == torch.int32 and table.dim() == 2 and table.shape[1] == 8, (table.dtype, table.shape)
+        return table
+    arr = np.ascontiguousarray(table, dtype=MIX_REC)
+    return torch.from_numpy(arr.view(np.int32).reshape(len(arr), 8).copy())
+
+
+def _mix_fields(table: torch.Tensor):
+    """(w, lam, box [N, 4] = y0 x0 y1 x1, label_b) of an int32 [N, 8] mix table, on its device."""
+    t = table.contiguous()
+    f = t[:, :2].contiguous().view(torch.float32)
+    return f[:, 0], f[:, 1], t[:, 2:6], t[:, 6]
 
 
 def _aligned16(*ts):
@@ -907,6 +939,47 @@ class HipBackend(_Common):
                                               _ptr(probs), _ptr(correct), _ptr(correct_k), self.stream()),
                    "drn_softmax_xent_ex")
 
+    def _mix_table(self, table, N):
+        assert table.dtype == torch.int32 and tuple(table.shape) == (N, 8) and table.is_contiguous()
+        assert table.device.type == self.device.type, "the mix table is read by the kernels: device memory"
+        if not getattr(self, "_mix_checked", False):
+            if self.L.drn_mix_rec_size() != MIX_REC.itemsize:
+                raise _lib.KernelLibraryError("MixRec layout mismatch between Python and the kernel library")
+            self._mix_checked = True
+        return table.data_ptr()
+
+    def softmax_xent_mix(self, logits, labels, table, grad_scale, dlogits, loss, correct, probs=None, smoothing=0.0,
+                         top_k=1, correct_k=None):
+        """softmax_xent_ex against the Mixup / CutMix target (1 - smoothing) (lam [j == labels[n]] +
+        (1 - lam) [j == label_b]) + smoothing / ncls, lam and label_b from sample n's record of `table`
+        (int32 [N, 8] device tensor, MIX_REC), read when the kernel runs; correct / correct_k count
+        against the dominant label (labels[n] if lam >= 0.5 else label_b). One launch (head.hip
+        softmax_xent_mix_kernel); lam == 1 everywhere gives softmax_xent_ex's bits."""
+        N, ncls = logits.shape
+        assert logits.dtype == loss.dtype == torch.float32 and labels.dtype == torch.int32
+        assert logits.is_contiguous() and labels.numel() == N and loss.numel() == N
+        for t, dt, n in ((dlogits, torch.float32, N * ncls), (probs, torch.float32, N * ncls),
+                         (correct, torch.int32, N), (correct_k, torch.int32, N)):
+            assert t is None or (t.dtype == dt and t.numel() == n and t.is_contiguous())
+        _lib.check(self.L.drn_softmax_xent_mix(logits.data_ptr(), labels.data_ptr(), self._mix_table(table, N), N,
+                                               ncls, float(grad_scale), float(smoothing), int(top_k), _ptr(dlogits),
+                                               loss.data_ptr(), _ptr(probs), _ptr(correct), _ptr(correct_k),
+                                               self.stream()), "drn_softmax_xent_mix")
+
+    def mix_pairs(self, src, dst, table):
+        """Mixup / CutMix of the batch src [N, H, W, 8] bf16 with its reversal into dst, sample n by its
+        record of `table` (int32 [N, 8] device tensor, MIX_REC; see mix.hip). dst is src (in place:
+        unchanged pixels are not stored) or a tensor that does not overlap it."""
+        assert src.dim() == 4 and src.shape[-1] == 8 and src.shape == dst.shape, (src.shape, dst.shape)
+        assert src.dtype == dst.dtype == torch.bfloat16 and src.is_contiguous() and dst.is_contiguous()
+        N, H, W, _ = src.shape
+        if dst.data_ptr() != src.data_ptr():
+            nb = src.numel() * 2
+            assert dst.data_ptr() + nb <= src.data_ptr() or src.data_ptr() + nb <= dst.data_ptr(), \
+                "mix_pairs: dst must be src or not overlap it"
+        _lib.check(self.L.drn_mix_pairs(src.data_ptr(), dst.data_ptr(), self._mix_table(table, N), N, H * W, W,
+                                        self.stream()), "drn_mix_pairs")
+
     def colsum(self, x, out, scale=1.0, accumulate=False):
         rows, cols = x.shape
         _lib.check(self.L.drn_colsum(x.data_ptr(), rows, cols, out.data_ptr(), float(scale), int(accumulate),
@@ -1297,6 +1370,62 @@ class RefBackend(_Common):
             before = torch.arange(K, device=logits.device)[None, :] < lab[:, None]
             rank = (logits > zy).sum(1) + ((logits == zy) & before).sum(1)
             correct_k.copy_(((rank < top_k) & ~torch.isnan(zy[:, 0])).int())
+
+    def softmax_xent_mix(self, logits, labels, table, grad_scale, dlogits, loss, correct, probs=None, smoothing=0.0,
+                         top_k=1, correct_k=None):
+        """HipBackend.softmax_xent_mix's contract in torch, in the reference dtype (the oracle). A
+        record with lam == 1 does not look at its label_b; the rank is taken on the logits as given."""
+        if not 0.0 <= smoothing < 1.0 or top_k < 1:
+            raise ValueError(f"softmax_xent_mix needs 0 <= smoothing < 1 and top_k >= 1, got {smoothing}, {top_k}")
+        N, K = logits.shape
+        _, lam32, _, lab_b = _mix_fields(mix_table_tensor(table))
+        assert lam32.numel() == N, (lam32.numel(), N)
+        lam = lam32.to(_DT[0])
+        la = labels.long()
+        lb = torch.where(lam32 == 1.0, la, lab_b.long())   # (unused at lam == 1: any in-range class)
+        z = logits.to(_DT[0])
+        d = z - z.max(1, keepdim=True)[0]
+        e = d.exp()
+        se = e.sum(1)
+        da, db = d.gather(1, la[:, None])[:, 0], d.gather(1, lb[:, None])[:, 0]
+        ls = se.log() - (1.0 - smoothing) * (lam * da + (1.0 - lam) * db)
+        if smoothing != 0.0:
+            ls = ls - (smoothing / K) * d.sum(1)
+        loss.copy_(ls)
+        p = e / se[:, None]
+        if probs is not None:
+            probs.copy_(p)
+        if dlogits is not None:
+            t = lam[:, None] * F.one_hot(la, K).to(_DT[0]) + (1.0 - lam)[:, None] * F.one_hot(lb, K).to(_DT[0])
+            dlogits.copy_((p - (1.0 - smoothing) * t - smoothing / K) * grad_scale)
+        dom = torch.where(lam32 >= 0.5, la, lb)
+        if correct is not None:
+            correct.copy_((logits.argmax(1) == dom).int())
+        if correct_k is not None:
+            zy = logits.gather(1, dom[:, None])
+            before = torch.arange(K, device=logits.device)[None, :] < dom[:, None]
+            rank = (logits > zy).sum(1) + ((logits == zy) & before).sum(1)
+            correct_k.copy_(((rank < top_k) & ~torch.isnan(zy[:, 0])).int())
+
+    def mix_pairs(self, src, dst, table):
+        """HipBackend.mix_pairs's contract in torch, in the reference dtype: dst[n] = src[N-1-n] inside
+        sample n's box, w * src[n] + (1 - w) * src[N-1-n] elsewhere (src[n] / src[N-1-n] themselves at
+        w == 1 / w == 0); the middle sample of an odd batch is copied. dst may be src."""
+        assert src.dim() == 4 and src.shape == dst.shape, (src.shape, dst.shape)
+        N, H, W, _ = src.shape
+        w32, _, box, _ = _mix_fields(mix_table_tensor(table))
+        assert w32.numel() == N, (w32.numel(), N)
+        a = src.to(_DT[0])          # (a copy when dst is src: every read precedes every write)
+        b = a.flip(0)
+        w = w32.to(_DT[0])[:, None, None, None]
+        out = torch.where(w == 1.0, a, torch.where(w == 0.0, b, w * a + (1.0 - w) * b))
+        ys, xs = torch.arange(H)[None, :, None], torch.arange(W)[None, None, :]
+        y0, x0, y1, x1 = (box[:, i].long()[:, None, None] for i in range(4))
+        inbox = (ys >= y0) & (ys < y1) & (xs >= x0) & (xs < x1)
+        out = torch.where(inbox[..., None], b, out)
+        if N % 2:
+            out[N // 2] = a[N // 2]
+        dst.copy_(out)
 
     def colsum(self, x, out, scale=1.0, accumulate=False):
         s = x.sum(0) * scale

@@ -106,8 +106,14 @@ class Executor:
                  weight_decay: float = 2e-4, momentum: float = 0.9, params: ParamStore | None = None,
                  materialize_bn: Optional[bool] = None, optimizer: str = "momentum", lars_eta: float = 0.001,
                  lars_eps: float = 1e-9, label_smoothing: float = 0.0, top_k: int = 0, ema_decay: float = 0.0,
-                 ema_warmup: bool = True):
+                 ema_warmup: bool = True, mix: bool = False):
         self.spec, self.N, self.be = spec, batch, backend
+        # mix: the training target is mixed from two labels per sample (Mixup / CutMix): mix_table
+        # holds one record per sample (ops/backend.py MIX_REC; set_mix), in device memory like the
+        # LR, and the training forward's loss kernel reads lam and the second label from it
+        # (softmax_xent_mix). The images are mixed by the feeder (be.mix_pairs). False: no table,
+        # and the step makes exactly the calls it made before
+        self.mix = bool(mix)
         # "momentum": the reference's MomentumOptimizer; "lars": the same update with each conv /
         # dense kernel's gradient (weight decay included) scaled by its layer-wise trust ratio
         # eta * ||w|| / (||g|| + wd * ||w|| + eps) (csrc/kernels/sgd.hip), for large global batches
@@ -392,6 +398,10 @@ class Executor:
             g0 = self.stem_op.geom
             self.stem_geom4 = ConvGeom(g0.stride, g0.pad_h, g0.pad_w - 1, 1)
         self.labels = torch.zeros(N, dtype=torch.int32, device=self.device)
+        self.mix_table = None
+        if self.mix:
+            from ..ops.backend import mix_identity, mix_table_tensor
+            self.mix_table = mix_table_tensor(mix_identity(N)).to(self.device)
         hs = sp.stem_hw
         # fused stem conv + max-pool (DRN_STEM_POOL=0: the conv and pooling kernels separately):
         # the ImageNet stem geometry (7x7/2 packed, 3x3/2 pool without leading pad)
@@ -677,7 +687,12 @@ class Executor:
         be.sgemm(0, 1, N, ncls, C, 1.0, self.pooled, C, self.dense_w, C, 0.0, self.logits, ncls, bias=self.dense_b)
         # (evaluation loss is the plain cross-entropy: smoothing shapes the training target only)
         smoothing = self.label_smoothing if train else 0.0
-        if smoothing == 0.0 and self.top_k < 2:
+        if self.mix and train:
+            # (evaluation never mixes: the branches below, against ex.labels alone)
+            be.softmax_xent_mix(self.logits, self.labels, self.mix_table, 1.0 / N, self.dlogits, self.loss_vec,
+                                self.correct, smoothing=smoothing, top_k=max(self.top_k, 1),
+                                correct_k=self.correct_k)
+        elif smoothing == 0.0 and self.top_k < 2:
             be.softmax_xent(self.logits, self.labels, 1.0 / N, self.dlogits if train else None, self.loss_vec,
                             self.correct)
         else:
@@ -686,6 +701,18 @@ class Executor:
                                correct_k=self.correct_k)
         if self.check_nan:
             self._check(self.loss_vec, "cross-entropy")
+
+    def set_mix(self, table):
+        """The mix table of the batch now in ex.images / ex.labels: numpy MIX_REC [N] or an int32
+        [N, 8] tensor (ops/backend.py). Copied into mix_table, the device buffer the recorded loss
+        kernel reads, in stream order (a device tensor: no host synchronization)."""
+        if self.mix_table is None:
+            raise RuntimeError("this executor does not mix (Executor(mix=False))")
+        from ..ops.backend import mix_table_tensor
+        t = mix_table_tensor(table)
+        if tuple(t.shape) != (self.N, 8):
+            raise ValueError(f"the mix table has {t.shape[0]} records, the batch {self.N} samples")
+        self.mix_table.copy_(t, non_blocking=True)
 
     def _check(self, t: torch.Tensor, what: str):
         """DRN_CHECK_NAN=1 debug mode: synchronous finiteness check naming the failing stage."""
@@ -1186,7 +1213,9 @@ class Executor:
         """Loss and precision of the last forward. After a training forward with label_smoothing > 0,
         cross_entropy and cost are the smoothed loss (the objective being minimised), which is at
         least the entropy of the smoothed target; an evaluation forward reports the plain
-        cross-entropy. precision_top_k is present only when top_k >= 2."""
+        cross-entropy. precision_top_k is present only when top_k >= 2. After a training forward with
+        mix=True the loss is the mixed-target loss and both precisions count the dominant label
+        (the sample's own if lam >= 0.5, else its partner's)."""
         xent = float(self.loss_vec.double().mean())
         prec = float(self.correct.double().mean())
         l2 = float(self.P.trainable_l2())

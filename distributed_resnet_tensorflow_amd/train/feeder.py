@@ -5,6 +5,11 @@ previous step's compute) -> GPU preprocessing kernel (CIFAR crop/flip/standardiz
 fused VGG resize/crop/flip/mean-sub) writing NHWC bf16 (C padded to 8) straight into
 `executor.images`. CPU path: the reference backend runs the same preprocessing in fp32.
 Synthetic mode fills the device batch once (benchmarks: BASELINE "synthetic data").
+
+Mixup / CutMix (training feeders given a data.mix.MixSampler): the batch's mix table is drawn with
+the batch and staged with its other copies; after the preprocess kernel the images are mixed in
+place with their reversal (csrc/kernels/mix.hip) and the table goes to the executor, whose loss
+kernel reads it. `state()` then carries `mix_batch`, the number of draws consumed.
 """
 from __future__ import annotations
 
@@ -16,21 +21,43 @@ import torch
 from ..data import cifar as cifar_data
 
 
+def _mix_host_table(sampler, index: int, labels, pin: bool):
+    """The int32 [N, 8] host tensor (page-locked when `pin`) of sampler.draw(index, labels)."""
+    from ..ops.backend import mix_table_tensor
+    t = mix_table_tensor(sampler.draw(index, labels.numpy() if isinstance(labels, torch.Tensor) else labels))
+    return t.pin_memory() if pin else t
+
+
 class SyntheticFeeder:
-    def __init__(self, ex, seed: int = 0):
-        self.ex = ex
+    """mix (a data.mix.MixSampler): the static batch stays in a buffer of the feeder's own and every
+    next() mixes it, with the draw of that batch, out of place into ex.images (mixing the static
+    batch in place would compound from step to step)."""
+
+    def __init__(self, ex, seed: int = 0, mix=None, mix_index: int = 0):
+        self.ex, self.mix, self._mix_index = ex, mix, int(mix_index)
         ex.be.synthetic_images(ex.images, seed)
         g = torch.Generator().manual_seed(seed)
-        ex.labels.copy_(torch.randint(0, ex.spec.num_classes, (ex.N,), generator=g, dtype=torch.int32))
+        self.h_labels = torch.randint(0, ex.spec.num_classes, (ex.N,), generator=g, dtype=torch.int32)
+        ex.labels.copy_(self.h_labels)
+        if mix is not None:
+            self.pristine = ex.images.clone()
+            self.d_table = torch.empty(ex.N, 8, dtype=torch.int32, device=ex.device)
 
     def next(self):
+        if self.mix is not None:
+            ex = self.ex
+            self.d_table.copy_(_mix_host_table(self.mix, self._mix_index, self.h_labels, ex.device.type == "cuda"),
+                               non_blocking=True)
+            ex.be.mix_pairs(self.pristine, ex.images, self.d_table)
+            ex.set_mix(self.d_table)
+            self._mix_index += 1
         return True
 
     def prefetch(self):
         pass
 
     def state(self):
-        return {}
+        return {"mix_batch": self._mix_index} if self.mix is not None else {}
 
     def close(self):
         pass
@@ -76,8 +103,14 @@ class _StagedFeeder:
     COPY_STREAM = True
     COPY_STREAM_PRIORITY = -1
 
-    def _init_staging(self, ex):
+    def _init_staging(self, ex, mix=None, mix_index: int = 0):
+        """mix (a data.mix.MixSampler, training feeders only): batch i of this feeder is mixed with
+        the sampler's draw mix_index + i. The table is drawn and staged with the batch's other
+        copies; _consume mixes ex.images in place after the preprocess kernel and hands the table to
+        the executor. state() then carries `mix_batch`, the draws consumed so far."""
         self.ex = ex
+        self.mix, self._mix_index = mix, int(mix_index)
+        self.d_table = torch.empty(ex.N, 8, dtype=torch.int32, device=ex.device) if mix is not None else None
         self.gpu = ex.device.type == "cuda"
         prio = int(os.environ.get("DRN_COPY_STREAM_PRIORITY", str(self.COPY_STREAM_PRIORITY)))
         self.copy_stream = (torch.cuda.Stream(device=ex.device, priority=prio)
@@ -86,9 +119,30 @@ class _StagedFeeder:
         self._consumed = None          # event after the preprocess of the batch last handed out
         self._main = None              # the stream that consumes the batches (set by next())
         self._need_prefetch = False
-        self._pending_state, self._pending_valid = self.loader.state(), ex.N
-        self._state, self.valid = self.loader.state(), ex.N
+        self._pending_state, self._pending_valid = self._loader_state(), ex.N
+        self._state, self.valid = self._loader_state(), ex.N
         self._exhausted = False
+
+    def _loader_state(self):
+        """The loader's cursors, and with mixing the number of draws used up to that position."""
+        st = self.loader.state()
+        if self.mix is not None:
+            st["mix_batch"] = self._mix_index
+        return st
+
+    def _mix_pairs(self, labels):
+        """[(device table, host table)] of the batch being staged (empty without mixing)."""
+        if self.mix is None:
+            return []
+        t = _mix_host_table(self.mix, self._mix_index, labels, self.gpu)
+        self._mix_index += 1
+        return [(self.d_table, t)]
+
+    def _mix_consume(self):
+        """After the preprocess kernel: mix ex.images in place, hand the table to the executor."""
+        if self.mix is not None:
+            self.ex.be.mix_pairs(self.ex.images, self.ex.images, self.d_table)
+            self.ex.set_mix(self.d_table)
 
     def _stage(self, pairs):
         """pairs: [(device dst, host src)]; enqueues the copies on the copy stream (or, without
@@ -122,9 +176,9 @@ class _StagedFeeder:
         except StopIteration:
             self._exhausted = True
             return
-        self._pending_state = self.loader.state()
         self._pending_valid = int(getattr(self.loader, "valid", self.ex.N))
         self._stage_item(item)
+        self._pending_state = self._loader_state()   # (after the batch, its mix draw included)
 
     def _wait(self):
         if self.gpu and self._pending is not None:
@@ -162,26 +216,27 @@ class _StagedFeeder:
 class CifarFeeder(_StagedFeeder):
     COPY_STREAM = False
 
-    def __init__(self, ex, loader: "cifar_data.CifarLoader", is_training: bool):
+    def __init__(self, ex, loader: "cifar_data.CifarLoader", is_training: bool, mix=None, mix_index: int = 0):
         self.loader, self.train = loader, is_training
         N, dev = ex.N, ex.device
         self.d_img = torch.empty(N, 32, 32, 3, dtype=torch.uint8, device=dev)
         self.d_par = torch.empty(N, 3, dtype=torch.int32, device=dev)
         self.d_lab = torch.empty(N, dtype=torch.int32, device=dev)
-        self._init_staging(ex)
+        self._init_staging(ex, mix if is_training else None, mix_index)   # (evaluation never mixes)
         self._prefetch()
 
     def _stage_item(self, item):
         imgs, labels, params = item
-        self._stage([(self.d_img, imgs), (self.d_par, params), (self.d_lab, labels)])
+        self._stage([(self.d_img, imgs), (self.d_par, params), (self.d_lab, labels)] + self._mix_pairs(labels))
 
     def _consume(self):
         self.ex.be.cifar_augment(self.d_img, self.d_par, self.ex.images, cifar_data.PAD)
         self.ex.labels.copy_(self.d_lab)
+        self._mix_consume()
 
 
 class ImagenetFeeder(_StagedFeeder):
-    def __init__(self, ex, loader, is_training: bool, max_bytes: int = 64 << 20):
+    def __init__(self, ex, loader, is_training: bool, max_bytes: int = 64 << 20, mix=None, mix_index: int = 0):
         from ..data import imagenet as inet
         self.inet = inet
         self.loader = loader
@@ -190,7 +245,7 @@ class ImagenetFeeder(_StagedFeeder):
         self.d_lab = torch.empty(ex.N, dtype=torch.int32, device=ex.device)
         self.h_packed = None  # CPU path: the reference backend preprocesses from host memory
         self.h_desc = None
-        self._init_staging(ex)
+        self._init_staging(ex, mix if is_training else None, mix_index)   # (evaluation never mixes)
         self._prefetch()
 
     def _stage_item(self, item):
@@ -202,6 +257,7 @@ class ImagenetFeeder(_StagedFeeder):
             self.h_packed = packed
             self.h_desc = desc.numpy().view(self.inet.IMG_DESC) if isinstance(desc, torch.Tensor) else desc
             self.d_lab.copy_(_as_tensor(labels))
+            self._stage(self._mix_pairs(labels))
             return
         if n > self.d_buf.numel():
             # reallocation (prefetch may run on a worker thread, whose current stream is NOT the
@@ -218,7 +274,8 @@ class ImagenetFeeder(_StagedFeeder):
                 self.d_buf.record_stream(self.copy_stream)
             if self._main is not None:
                 self.d_buf.record_stream(self._main)
-        self._stage([(self.d_buf[:n], packed), (self.d_desc, desc_bytes), (self.d_lab, labels)])
+        self._stage([(self.d_buf[:n], packed), (self.d_desc, desc_bytes), (self.d_lab, labels)]
+                    + self._mix_pairs(labels))
 
     def _consume(self):
         if self.gpu:
@@ -226,3 +283,4 @@ class ImagenetFeeder(_StagedFeeder):
         else:
             self.ex.be.vgg_preprocess(self.h_packed, self.h_desc, self.ex.images, self.inet.RGB_MEANS)
         self.ex.labels.copy_(self.d_lab)
+        self._mix_consume()

@@ -4,7 +4,8 @@
                   ImageNet 40) + throughput (images/sec, steps/sec) — the reference has no timer
                   (SURVEY Q17); optional metrics.jsonl. --top_k=K adds `precision@K`.
   SummaryHook     SummarySaverHook(save_steps=100): cross_entropy, cost, learning_rate,
-                  Precision (+ images/sec; + Precision@K with --top_k=K) as tfevents (chief only).
+                  Precision (+ images/sec; + Precision@K with --top_k=K; + mix/lam, the batch mean of
+                  the target weight, with --mixup_alpha / --cutmix_alpha) as tfevents (chief only).
   CheckpointHook  MonitoredTrainingSession(save_checkpoint_secs=60) saver (chief only).
   StopAtStepHook  StopAtStepHook(last_step=train_steps) (the reference CIFAR main never stops:
                   SURVEY Q5; here --train_steps is honoured).
@@ -101,6 +102,8 @@ class SummaryHook(Hook):
             scalars[f"Precision@{_top_k(sess)}"] = m["precision_top_k"]
         if "ema_decay" in m:  # (--ema_decay > 0: the last update's effective decay, warm-up included)
             scalars["ema/decay"] = m["ema_decay"]
+        if "mix_lam" in m:    # (--mixup_alpha / --cutmix_alpha: the batch mean of the target weight lam)
+            scalars["mix/lam"] = m["mix_lam"]
         ex = getattr(sess, "ex", None)
         if getattr(ex, "optimizer", "momentum") == "lars":
             # the last update's trust ratios of the adapting (conv / dense kernel) slots

@@ -80,7 +80,7 @@ class TrainingSession:
                  collective_timeout_s: float = 0.0, precision: str = "bf16", shard_optimizer: bool = False,
                  step_trial: bool = True, optimizer: str = "momentum", lars_eta: float = 0.001,
                  lars_eps: float = 1e-9, label_smoothing: float = 0.0, top_k: int = 0, ema_decay: float = 0.0,
-                 ema_warmup: bool = True):
+                 ema_warmup: bool = True, mix: bool = False):
         self.cluster = cluster
         self.spec = spec
         self.device = torch.device(cluster.device)
@@ -88,7 +88,7 @@ class TrainingSession:
         self.ex = Executor(spec, batch, self.be, self.device, seed=seed, weight_decay=weight_decay,
                            optimizer=optimizer, lars_eta=lars_eta, lars_eps=lars_eps,
                            label_smoothing=label_smoothing, top_k=top_k, ema_decay=ema_decay,
-                           ema_warmup=ema_warmup)
+                           ema_warmup=ema_warmup, mix=mix)
         self.lr = lr_schedule
         self.meta = meta or {}
         # DRN_FORCE_DP=1: the data-parallel engine on a single-rank process group (profiling the
@@ -466,6 +466,9 @@ class TrainingSession:
             m["learning_rate"] = self.cur_lr
             if self.ex.ema_decay > 0:
                 m["ema_decay"] = self.cur_ema_decay   # the effective d_t of the last update
+            if self.ex.mix_table is not None:
+                # the batch mean of lam of the last step's mix table (column 1 holds lam's bits)
+                m["mix_lam"] = float(self.ex.mix_table[:, 1].contiguous().view(torch.float32).double().mean())
             if self.engine is not None:
                 m.update(self.engine.stats())
                 self._guard(self.engine.check_errors)

@@ -54,14 +54,35 @@ def _meta(FLAGS, spec):
             "num_classes": spec.num_classes,
             "spec_name": spec.name,
             "optimizer": FLAGS.optimizer, "eta": FLAGS.lars_eta, "eps": FLAGS.lars_eps,
-            "label_smoothing": FLAGS.label_smoothing, "ema_decay": FLAGS.ema_decay}
+            "label_smoothing": FLAGS.label_smoothing, "ema_decay": FLAGS.ema_decay,
+            "mixup_alpha": FLAGS.mixup_alpha, "cutmix_alpha": FLAGS.cutmix_alpha}
+
+
+def mixing(FLAGS) -> bool:
+    """Whether the flags turn Mixup / CutMix on."""
+    return FLAGS.mixup_alpha > 0 or FLAGS.cutmix_alpha > 0
+
+
+def make_mix_sampler(FLAGS, ex, cluster):
+    """The MixSampler of a training feeder (None with mixing off): the sampler's rank is the cluster
+    rank, so every data-parallel replica mixes its own shard with its own draws."""
+    if not mixing(FLAGS):
+        return None
+    from ..data.mix import MixSampler
+    img = ex.spec.image_size
+    return MixSampler(ex.N, img, img, mixup_alpha=FLAGS.mixup_alpha, cutmix_alpha=FLAGS.cutmix_alpha,
+                      prob=FLAGS.mix_prob, switch_prob=FLAGS.mix_switch_prob, per_sample=FLAGS.mix_per_sample,
+                      seed=FLAGS.seed, rank=cluster.rank)
 
 
 def make_feeder(FLAGS, ex, cluster, is_training: bool, data_state=None, batch=None):
     bs = batch or ex.N
-    if FLAGS.synthetic_data:
-        return SyntheticFeeder(ex, seed=FLAGS.seed + 101 * cluster.rank)
     ds = data_state or {}
+    # (training feeders only: evaluation never mixes)
+    mix = dict(mix=make_mix_sampler(FLAGS, ex, cluster), mix_index=int(ds.get("mix_batch", 0))) \
+        if is_training and mixing(FLAGS) else {}
+    if FLAGS.synthetic_data:
+        return SyntheticFeeder(ex, seed=FLAGS.seed + 101 * cluster.rank, **mix)
     gpu = ex.device.type == "cuda"
     pin = dict(pin=gpu, pin_device=ex.device if gpu else None)
     if FLAGS.dataset in ("cifar10", "cifar100"):
@@ -70,7 +91,7 @@ def make_feeder(FLAGS, ex, cluster, is_training: bool, data_state=None, batch=No
         loader = cifar_data.CifarLoader(recs, bs, is_training, seed=FLAGS.seed, rank=cluster.rank,
                                         world=cluster.world, epoch=int(ds.get("data_epoch", 0)),
                                         cursor=int(ds.get("data_cursor", 0)), **pin)
-        return CifarFeeder(ex, loader, is_training)
+        return CifarFeeder(ex, loader, is_training, **mix)
     from ..data import imagenet
     path = FLAGS.train_data_path if is_training else FLAGS.eval_data_path
     loader = imagenet.ImagenetLoader(path, bs, is_training, seed=FLAGS.seed, rank=cluster.rank, world=cluster.world,
@@ -78,7 +99,7 @@ def make_feeder(FLAGS, ex, cluster, is_training: bool, data_state=None, batch=No
                                      num_epochs=FLAGS.num_epochs if is_training else 1,
                                      epoch=int(ds.get("data_epoch", 0)), cursor=int(ds.get("data_cursor", 0)),
                                      batch_index=int(ds.get("data_batch", 0)), workers=FLAGS.input_workers, **pin)
-    return ImagenetFeeder(ex, loader, is_training)
+    return ImagenetFeeder(ex, loader, is_training, **mix)
 
 
 def train(FLAGS, cluster=None):
@@ -112,7 +133,7 @@ def train(FLAGS, cluster=None):
                            shard_optimizer=FLAGS.optimizer_sharding, optimizer=FLAGS.optimizer,
                            lars_eta=FLAGS.lars_eta, lars_eps=FLAGS.lars_eps,
                            label_smoothing=FLAGS.label_smoothing, top_k=FLAGS.top_k, ema_decay=FLAGS.ema_decay,
-                           ema_warmup=FLAGS.ema_warmup)
+                           ema_warmup=FLAGS.ema_warmup, mix=mixing(FLAGS))
     feeder = make_feeder(FLAGS, sess.ex, cluster, True, sess.data_state)
     is_imagenet = FLAGS.dataset == "imagenet"
     hooks = [LoggingHook(FLAGS.log_every_n_steps, FLAGS.batch_size * cluster.world,
