@@ -24,7 +24,7 @@ __global__ __launch_bounds__(256) void cifar_augment_kernel(const uint8_t* __res
   const uint8_t* img = in + (size_t)n * HW * 3;
   constexpr int MAXP = 8;  // up to 2048 pixels per image with 256 threads
   float v[MAXP][3];
-  float s = 0.f, q = 0.f;
+  float s = 0.f;
 #pragma unroll
   for (int i = 0; i < MAXP; ++i) {
     const int pix = threadIdx.x + i * 256;
@@ -38,19 +38,31 @@ __global__ __launch_bounds__(256) void cifar_augment_kernel(const uint8_t* __res
         v[i][0] = p[0]; v[i][1] = p[1]; v[i][2] = p[2];
       }
       s += v[i][0] + v[i][1] + v[i][2];
-      q += v[i][0] * v[i][0] + v[i][1] * v[i][1] + v[i][2] * v[i][2];
     }
   }
   __shared__ float red[2][4];
   s = wave_sum(s);
-  q = wave_sum(q);
-  if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = s; red[1][threadIdx.x >> 6] = q; }
+  if ((threadIdx.x & 63) == 0) red[0][threadIdx.x >> 6] = s;
   __syncthreads();
-  s = red[0][0] + red[0][1] + red[0][2] + red[0][3];
-  q = red[1][0] + red[1][1] + red[1][2] + red[1][3];
+  s = red[0][0] + red[0][1] + red[0][2] + red[0][3];  // (integers below 2^24: exact)
   const float cnt = (float)(HW * 3);
   const float mean = s / cnt;
-  const float var = fmaxf(q / cnt - mean * mean, 0.f);
+  // variance as sum (v - mean)^2 / cnt over the pixels still in registers: E[x^2] - mean^2 on raw
+  // 0..255 values cancels to nothing in fp32 for a bright low-contrast image (mean^2 ~ 65000
+  // against a variance below 1)
+  float q = 0.f;
+#pragma unroll
+  for (int i = 0; i < MAXP; ++i) {
+    if (threadIdx.x + i * 256 < HW) {
+      const float d0 = v[i][0] - mean, d1 = v[i][1] - mean, d2 = v[i][2] - mean;
+      q += d0 * d0 + d1 * d1 + d2 * d2;
+    }
+  }
+  q = wave_sum(q);
+  if ((threadIdx.x & 63) == 0) red[1][threadIdx.x >> 6] = q;
+  __syncthreads();
+  q = red[1][0] + red[1][1] + red[1][2] + red[1][3];
+  const float var = q / cnt;
   const float adj = fmaxf(sqrtf(var), rsqrtf(cnt));
   const float inv = 1.f / adj;
 #pragma unroll

@@ -1448,7 +1448,10 @@ class RefBackend(_Common):
         xp = F.pad(xc, (pad_w, pr, pad_h, pb), value=float("-inf"))
         win = xp.unfold(2, k, stride).unfold(3, k, stride)  # N C P Q k k
         flat = win.reshape(N, C, P, Q, k * k)
-        v, i = flat.max(-1)
+        v = flat.max(-1)[0]
+        # the FIRST tap (row-major) holding the maximum, as the kernels' strict '>' scan records it
+        taps = torch.arange(k * k).expand_as(flat)
+        i = torch.where(flat == v.unsqueeze(-1), taps, torch.full_like(taps, k * k)).min(-1)[0]
         y.copy_(v.permute(0, 2, 3, 1))
         arg.copy_(i.permute(0, 2, 3, 1).to(torch.uint8))
 
@@ -1558,6 +1561,13 @@ class RefBackend(_Common):
         out.copy_(res)
 
     def synthetic_images(self, out, seed):
-        g = torch.Generator().manual_seed(int(seed))
+        """The hash noise of augment.hip synthetic_images_kernel (the same images as the HIP path):
+        element e = 3 * pixel + channel -> [-1, 1), in 64-bit integers masked to 32 bits."""
+        m32 = 0xFFFFFFFF
+        h = ((torch.arange(out.numel() // out.shape[-1] * 3, dtype=torch.int64) & m32) * 2654435761 & m32) \
+            ^ (int(seed) & m32)
+        h = ((h ^ (h >> 16)) * 0x7FEB352D) & m32
+        h = ((h ^ (h >> 15)) * 0x846CA68B) & m32     # (wraps in int64: the low 32 bits are right)
+        h = h ^ (h >> 16)
         out.zero_()
-        out[..., :3] = torch.rand(out.shape[:-1] + (3,), generator=g) * 2 - 1
+        out[..., :3] = ((h >> 8).double() * (2.0 / 16777216.0) - 1.0).view(out.shape[:-1] + (3,)).to(out.dtype)

@@ -753,6 +753,13 @@ def test_maxpool(hip, ref, H, pad):
         be.maxpool_bwd(dy.to(dev) if dev == "cuda" else dy.float(), arg, dx, 3, 2, pad, pad)
         out[be.name] = [y.float().cpu(), arg.cpu(), dx.float().cpu(), st.sum(0).cpu()]
     assert rel(out["hip"][0], out["ref"][0]) < 1e-3
+    # the argmax record: the reference backend's where the window has one maximum, the first maximum
+    # in row-major tap order (tests/kernel_refs.py) where it has several
+    from kernel_refs import maxpool_fwd as first_max
+    _, first, nmax = first_max(x.float(), 3, 2, pad, pad)
+    one = nmax == 1
+    assert torch.equal(out["hip"][1][one], out["ref"][1][one])
+    assert torch.equal(out["hip"][1][~one], first[~one])
     assert rel(out["hip"][2], out["ref"][2]) < 1e-2
     assert rel(out["hip"][3], out["ref"][3]) < 1e-3
 
