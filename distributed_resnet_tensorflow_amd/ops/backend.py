@@ -268,6 +268,15 @@ class _Common:
     def fill_(self, t, v: float):
         t.fill_(v)
 
+    @staticmethod
+    def _check_out_fill(y, residual, out_map, bn_bwd):
+        """out_fill (both backends): a plain strided output whose zero stores reach every other position."""
+        assert out_map is not None and bn_bwd is None and residual is None, "out_fill: plain strided output only"
+        # the zeros go to the sibling positions of the phase grid's pixels: they must be the whole output
+        # (an odd size with a phase other than 0 leaves its last row / column to no pixel)
+        assert out_map.P * out_map.stride >= y.shape[1] and out_map.Q * out_map.stride >= y.shape[2], \
+            "out_fill: the phase grid's sibling positions do not cover the output"
+
     # Consumer-side finalize (BnCfin) composed from the separate ops; HIP overrides with kernels
     # that finalize in their prologue.
     def _publish_fwd(self, f: BnCfin):
@@ -599,7 +608,7 @@ class HipBackend(_Common):
         in_fin: the input BN (in_bn) is finalized by this conv's prologue (BnCfin)."""
         a = self.conv_args(x, w, y, g, in_bn, relu_in, residual, stats, out_map, bn_bwd, bn_fin, in_fin)
         if out_fill:
-            assert out_map is not None and bn_bwd is None and residual is None, "out_fill: plain strided output only"
+            self._check_out_fill(y, residual, out_map, bn_bwd)
             a.out_fill = 1
         self.launch_conv(a)
 
@@ -1172,6 +1181,8 @@ class RefBackend(_Common):
 
     def conv_fwd(self, x, w, y, g: ConvGeom, in_bn=None, relu_in=True, residual=None, stats=None, out_map=None,
                  bn_bwd=None, bn_fin: Optional[BnFin] = None, out_fill: bool = False, in_fin: Optional[BnCfin] = None):
+        if out_fill:
+            self._check_out_fill(y, residual, out_map, bn_bwd)
         if in_fin is not None and in_fin.publish:
             self._publish_fwd(in_fin)
         self._conv_fwd(x, w, y, g, in_bn, relu_in, residual, stats, out_map, bn_bwd, out_fill)
@@ -1238,8 +1249,8 @@ class RefBackend(_Common):
     def bn_finalize(self, part, G, count, gamma, beta, run_mean, run_var, scale, shift, mean, invstd,
                     momentum, eps, update_running=True):
         C = gamma.numel()
-        p = part.view(-1)[:2 * C].view(2, C).double().clone()
-        part.view(-1)[:2 * C].zero_()
+        p = part.view(-1)[:G * 2 * C].view(G, 2, C).double().sum(0)   # (the G replicas, as the HIP finalize)
+        part.view(-1)[:G * 2 * C].zero_()
         mu = p[0] / count
         var = (p[1] / count - mu * mu).clamp_min(0)
         istd = 1.0 / torch.sqrt(var + eps)
@@ -1249,6 +1260,8 @@ class RefBackend(_Common):
         invstd.copy_(istd.to(_DT[0]))
         if update_running:
             unb = var * count / (count - 1) if count > 1 else var
+            # (momentum as the fp32 kernel argument it is on the HIP side; 1 - momentum is exact there)
+            momentum = float(np.float32(momentum))
             run_mean.mul_(momentum).add_((1 - momentum) * mu.to(_DT[0]))
             run_var.mul_(momentum).add_((1 - momentum) * unb.to(_DT[0]))
 
@@ -1284,8 +1297,8 @@ class RefBackend(_Common):
 
     def bn_finalize_bwd(self, part, G, count, gamma, invstd, dgamma, dbeta, coef):
         C = gamma.numel()
-        p = part.view(-1)[:2 * C].view(2, C).double().clone()
-        part.view(-1)[:2 * C].zero_()
+        p = part.view(-1)[:G * 2 * C].view(G, 2, C).double().sum(0)
+        part.view(-1)[:G * 2 * C].zero_()
         dbeta.copy_(p[0].to(_DT[0]))
         dgamma.copy_(p[1].to(_DT[0]))
         coef.view(3, C)[0].copy_(gamma * invstd)

@@ -24,6 +24,9 @@ def bf(t):
     return t.to(torch.bfloat16)
 
 
+SENT = -7.0   # prefill of every output a kernel must write whole: a stray or missing store shows
+
+
 CONV_CASES = [
     # N, H, W, C, K, R, stride, pad
     (2, 8, 8, 16, 16, 3, 1, 1),
@@ -61,7 +64,7 @@ def test_conv_fwd(hip, ref, case, fused):
     st_ref = torch.zeros(2 * K)
     ref.conv_fwd(x.float(), w.float(), y_ref, g, in_bn=in_bn, residual=None if res is None else res.float(),
                  stats=st_ref)
-    y = torch.zeros(N, P, P, K, dtype=torch.bfloat16, device="cuda")
+    y = torch.full((N, P, P, K), SENT, dtype=torch.bfloat16, device="cuda")
     st = torch.zeros(2, K, device="cuda")
     hip.conv_fwd(x.cuda(), w.cuda(), y, g,
                  in_bn=None if in_bn is None else (in_bn[0].cuda(), in_bn[1].cuda()),
@@ -136,7 +139,7 @@ def test_conv_fwd_glds_configs(hip, ref, case, cfg, pro):
     y_ref = torch.zeros(N, P, P, K)
     st_ref = torch.zeros(2 * K)
     ref.conv_fwd(x.float(), w.float(), y_ref, g, in_bn=in_bn, residual=res.float(), stats=st_ref)
-    y = torch.zeros(N, P, P, K, dtype=torch.bfloat16, device="cuda")
+    y = torch.full((N, P, P, K), SENT, dtype=torch.bfloat16, device="cuda")
     st = torch.zeros(3, 2, K, device="cuda")  # 3 atomic-spreading replicas
     a = hip.conv_args(x.cuda(), w.cuda(), y, g, residual=res.cuda(), stats=st,
                       in_bn=None if in_bn is None else (in_bn[0].cuda(), in_bn[1].cuda()))
@@ -182,7 +185,7 @@ def test_conv_fwd_splitk(hip, ref, case, cfg, ks):
     ref.conv_fwd(x.float(), w.float(), y_ref, g, in_bn=in_bn, residual=res.float(), stats=st_ref)
     outs = []
     for _ in range(2):
-        y = torch.zeros(N, P, P, K, dtype=torch.bfloat16, device="cuda")
+        y = torch.full((N, P, P, K), SENT, dtype=torch.bfloat16, device="cuda")
         st = torch.zeros(3, 2, K, device="cuda")
         a = hip.conv_args(x.cuda(), w.cuda(), y, g, residual=res.cuda(), stats=st,
                           in_bn=(in_bn[0].cuda(), in_bn[1].cuda()))
@@ -222,7 +225,7 @@ def test_conv_fwd_streamk(hip, ref, case, cfg, G):
     ref.conv_fwd(x.float(), w.float(), y_ref, g, in_bn=in_bn, residual=res.float(), stats=st_ref)
     outs = []
     for _ in range(2):
-        y = torch.zeros(N, P, P, K, dtype=torch.bfloat16, device="cuda")
+        y = torch.full((N, P, P, K), SENT, dtype=torch.bfloat16, device="cuda")
         st = torch.zeros(3, 2, K, device="cuda")
         a = hip.conv_args(x.cuda(), w.cuda(), y, g, residual=res.cuda(), stats=st,
                           in_bn=(in_bn[0].cuda(), in_bn[1].cuda()))
@@ -299,7 +302,7 @@ def test_conv_splitk_handoff_stress(hip, ref, cfg):
     bad = []
     for it in range(60):
         ks = (2, 3, 4, -3, -5, -7)[it % 6]
-        y = torch.zeros(N, H, W, K, dtype=torch.bfloat16, device="cuda")
+        y = torch.full((N, H, W, K), SENT, dtype=torch.bfloat16, device="cuda")
         a = hip.conv_args(xc, wc, y, g)
         a.cfg = cfg
         hip._set_ksplit(a, ks)
@@ -362,7 +365,7 @@ def test_conv_fwd_nk(hip, ref, case, i, pro):
     y_ref = torch.zeros(N, P, P, K)
     st_ref = torch.zeros(2 * K)
     ref.conv_fwd(x.float(), w.float(), y_ref, g, in_bn=in_bn, residual=res.float(), stats=st_ref)
-    y = torch.zeros(N, P, P, K, dtype=torch.bfloat16, device="cuda")
+    y = torch.full((N, P, P, K), SENT, dtype=torch.bfloat16, device="cuda")
     st = torch.zeros(3, 2, K, device="cuda")
     a = hip.conv_args(x.cuda(), w.cuda(), y, g, residual=res.cuda(), stats=st,
                       in_bn=None if in_bn is None else (in_bn[0].cuda(), in_bn[1].cuda()))
@@ -396,7 +399,7 @@ def test_conv_nk_bn_bwd_reduce(hip, ref, i, R):
     y_ref = torch.zeros(N, H, H, K)
     st_ref = torch.zeros(2 * K)
     ref.conv_fwd(dy.float(), wt.float(), y_ref, g, stats=st_ref, bn_bwd=(xb.float(), sc, sh, mu, istd))
-    y = torch.zeros(N, H, H, K, dtype=torch.bfloat16, device="cuda")
+    y = torch.full((N, H, H, K), SENT, dtype=torch.bfloat16, device="cuda")
     st = torch.zeros(2, K, device="cuda")
     a = hip.conv_args(dy.cuda(), wt.cuda(), y, g, stats=st,
                       bn_bwd=(xb.cuda(), sc.cuda(), sh.cuda(), mu.cuda(), istd.cuda()))
@@ -416,10 +419,10 @@ def test_conv_glds_out_map(hip, ref):
     x = bf(torch.randn(N, P, P, C))
     w = bf(torch.randn(K, 1, 1, C) * 0.1)
     om = OutMap(P=P, Q=P, stride=2, oh=1, ow=0)
-    y_ref = torch.zeros(N, 2 * P, 2 * P, K)
+    y_ref = torch.full((N, 2 * P, 2 * P, K), SENT)
     ref.conv_fwd(x.float(), w.float(), y_ref, ConvGeom(1, 0, 0), out_map=om)
     for cfg in list(range(23)) + sorted(BIG):
-        y = torch.zeros(N, 2 * P, 2 * P, K, dtype=torch.bfloat16, device="cuda")
+        y = torch.full((N, 2 * P, 2 * P, K), SENT, dtype=torch.bfloat16, device="cuda")
         a = hip.conv_args(x.cuda(), w.cuda(), y, ConvGeom(1, 0, 0), out_map=om)
         a.cfg = cfg
         hip.launch_conv(a)
@@ -471,7 +474,7 @@ def test_conv_fused_bn_bwd_reduce(hip, ref, cfg):
     st_ref = torch.zeros(2 * C)
     ref.conv_fwd(dy.float(), wt.float(), y_ref, g, residual=res.float(), stats=st_ref,
                  bn_bwd=(xb.float(), sc, sh, mu, istd))
-    y = torch.zeros(N, H, H, C, dtype=torch.bfloat16, device="cuda")
+    y = torch.full((N, H, H, C), SENT, dtype=torch.bfloat16, device="cuda")
     st = torch.zeros(2, C, device="cuda")
     a = hip.conv_args(dy.cuda(), wt.cuda(), y, g, residual=res.cuda(), stats=st,
                       bn_bwd=(xb.cuda(), sc.cuda(), sh.cuda(), mu.cuda(), istd.cuda()))
@@ -502,7 +505,7 @@ def test_conv_dgrad_matches_autograd(hip, case):
     y.backward(dy.float().permute(0, 3, 1, 2))
     dx_ref = x.grad
     wt = w.flip(1, 2).permute(3, 1, 2, 0).contiguous()  # [C][R][S][K]
-    dx = torch.zeros(N, H, W, C, dtype=torch.bfloat16, device="cuda")
+    dx = torch.full((N, H, W, C), SENT, dtype=torch.bfloat16, device="cuda")
     hip.conv_fwd(dy.cuda(), bf(wt).cuda(), dx, dgrad_geom(g, R, R))
     torch.cuda.synchronize()
     assert rel(dx, dx_ref) < 1e-2
@@ -520,7 +523,7 @@ def test_conv_wgrad(hip, ref, case, fused):
     in_bn = (torch.rand(C) + 0.5, torch.randn(C) * 0.1) if fused else None
     dw_ref = torch.zeros(K, R, R, C)
     ref.conv_wgrad(x.float(), dy.float(), dw_ref, g, in_bn=in_bn)
-    dw = torch.zeros(K, R, R, C, device="cuda")
+    dw = torch.full((K, R, R, C), SENT, device="cuda")
     ws = torch.zeros(max(1, hip.wgrad_ws_elems(N * P * P, K, R, R, C)), device="cuda")
     hip.conv_wgrad(x.cuda(), dy.cuda(), dw, g, in_bn=None if in_bn is None else (in_bn[0].cuda(), in_bn[1].cuda()),
                    ws=ws)
@@ -560,7 +563,7 @@ def test_conv_wgrad_pipelines(hip, ref, case, ns, fused):
     in_bn = (torch.rand(C) + 0.5, torch.randn(C) * 0.5) if fused else None
     dw_ref = torch.zeros(K, R, R, C)
     ref.conv_wgrad(x.float(), dy.float(), dw_ref, g, in_bn=in_bn)
-    dw = torch.zeros(K, R, R, C, device="cuda")
+    dw = torch.full((K, R, R, C), SENT, device="cuda")
     ws = torch.zeros(max(1, hip.wgrad_ws_elems(N * P * P, K, R, R, C)), device="cuda")
     old = hip.forced_wgrad_ns
     hip.forced_wgrad_ns = ns
@@ -588,7 +591,7 @@ def test_conv_wgrad_large_splitk(hip, ref):
     g = ConvGeom(1, 1, 1)
     dw_ref = torch.zeros(K, 3, 3, C)
     ref.conv_wgrad(x.float(), dy.float(), dw_ref, g)
-    dw = torch.zeros(K, 3, 3, C, device="cuda")
+    dw = torch.full((K, 3, 3, C), SENT, device="cuda")
     ws = torch.zeros(max(1, hip.wgrad_ws_elems(N * H * H, K, 3, 3, C)), device="cuda")
     hip.conv_wgrad(x.cuda(), dy.cuda(), dw, g, ws=ws)
     torch.cuda.synchronize()
@@ -1067,7 +1070,7 @@ def test_fused_stem_conv_pool(hip, ref, N, H, pad):
     hip.stem_pack_weights(w.cuda(), w4)
     g4 = ConvGeom(stride=2, pad_h=pad, pad_w=pad - 1)
     # two-kernel path
-    y = torch.zeros(N, P, P, K, dtype=torch.bfloat16, device="cuda")
+    y = torch.full((N, P, P, K), SENT, dtype=torch.bfloat16, device="cuda")
     hip.conv_fwd(xp, w4, y, g4)
     yp_ref = torch.zeros(N, PP, PP, K, dtype=torch.bfloat16, device="cuda")
     arg_ref = torch.zeros(N, PP, PP, K, dtype=torch.uint8, device="cuda")
@@ -1136,7 +1139,7 @@ def test_packed_stem(hip, ref, N, H):
     assert torch.equal(w4[:, :, :7, :].cpu(), w[..., :4]) and w4[:, :, 7].abs().max().item() == 0
     ran = 0
     for cfg in range(hip.L.drn_conv_glds_num_cfgs()):
-        y = torch.zeros(N, P, P, K, dtype=torch.bfloat16, device="cuda")
+        y = torch.full((N, P, P, K), SENT, dtype=torch.bfloat16, device="cuda")
         st = torch.zeros(2, 2, K, device="cuda")
         a = hip.conv_args(xp, w4, y, g4, stats=st)
         a.cfg = cfg
