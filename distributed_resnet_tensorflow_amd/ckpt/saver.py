@@ -168,8 +168,9 @@ class Saver:
     @staticmethod
     def restore_meta(prefix: str) -> dict:
         """The checkpoint's `.meta` model description with the keys later versions added filled in
-        (label_smoothing, ema_decay, mixup_alpha and cutmix_alpha: 0, what every checkpoint without
-        the key was trained with); {} plus those defaults when the file is missing or unreadable."""
+        (label_smoothing, ema_decay, clip_grad_norm, mixup_alpha and cutmix_alpha: 0, and
+        skip_nonfinite_grads: False, what every checkpoint without the key was trained with); {} plus
+        those defaults when the file is missing or unreadable."""
         try:
             with open(prefix + ".meta") as f:
                 meta = dict(json.load(f))
@@ -177,6 +178,8 @@ class Saver:
             meta = {}
         meta["label_smoothing"] = float(meta.get("label_smoothing", 0.0))
         meta["ema_decay"] = float(meta.get("ema_decay", 0.0))
+        meta["clip_grad_norm"] = float(meta.get("clip_grad_norm", 0.0))
+        meta["skip_nonfinite_grads"] = bool(meta.get("skip_nonfinite_grads", False))
         meta["mixup_alpha"] = float(meta.get("mixup_alpha", 0.0))
         meta["cutmix_alpha"] = float(meta.get("cutmix_alpha", 0.0))
         return meta

@@ -176,6 +176,15 @@ def validate(fv: "FlagValues") -> None:
         raise FlagsError(f"--mix_switch_prob must be in [0, 1], got {fv.mix_switch_prob!r}")
     if (fv.mixup_alpha > 0 or fv.cutmix_alpha > 0) and fv.model == "lrnet":
         raise FlagsError("--mixup_alpha / --cutmix_alpha are not supported by --model=lrnet")
+    if not fv.clip_grad_norm >= 0.0 or fv.clip_grad_norm == float("inf"):
+        raise FlagsError(f"--clip_grad_norm must be a finite value >= 0, got {fv.clip_grad_norm!r}")
+    if fv.clip_grad_norm > 0 or fv.skip_nonfinite_grads:
+        if fv.optimizer_sharding:
+            raise FlagsError("--clip_grad_norm / --skip_nonfinite_grads cannot be combined with "
+                             "--optimizer_sharding: a shard sees only part of the gradient and both need its "
+                             "global norm")
+        if fv.model == "lrnet":
+            raise FlagsError("--clip_grad_norm / --skip_nonfinite_grads are not supported by --model=lrnet")
 
 
 FLAGS = FlagValues()
@@ -290,7 +299,12 @@ def define_reference_flags(flag_values: FlagValues = FLAGS, **defaults) -> FlagV
     Fl("mix_prob", 1.0, "Probability that a training batch is mixed (--mixup_alpha / --cutmix_alpha).", fv)
     Fl("mix_switch_prob", 0.5, "With both --mixup_alpha and --cutmix_alpha on: probability of CutMix.", fv)
     B("mix_per_sample", False, "Draw the mix kind, lam and box per sample instead of once per batch.", fv)
-    I("collective_timeout_secs", 600, "Process-group timeout and collective-watchdog limit: a rank whose "
+    Fl("clip_grad_norm", 0.0, "c > 0: scale the (averaged) gradient by c / max(norm, c), norm its global L2 norm "
+       "(TF's clip_by_global_norm), computed and applied on the device in front of the optimizer; 0 = off.", fv)
+    B("skip_nonfinite_grads", False, "Skip the update of a step whose gradient holds a NaN or Inf (global norm not "
+      "finite): weights, momentum, EMA and LARS trust ratios stay as they were; global_step and the LR schedule "
+      "still advance, BatchNorm moving statistics keep the step's update.", fv)
+    I("collective_timeout_secs", 600,"Process-group timeout and collective-watchdog limit: a rank whose "
       "gradient exchange stalls this long exits (the launcher restarts the job from its checkpoint).", fv)
     I("fault_inject_step", -1, "Kill this process at the given global step (fault-injection tests).", fv)
     I("fault_inject_rank", 0, "Rank that --fault_inject_step applies to.", fv)

@@ -134,6 +134,12 @@ _SIGS = {
     "drn_sgd_momentum_ema": ([c_p, c_p, c_p, c_int, c_p, c_i64, c_p, c_f, c_f, c_f, c_p, c_p, c_p, c_p], c_int),
     "drn_lars_momentum_ema": ([c_p, c_p, c_p, c_int, c_p, c_p, c_int, c_int, c_p, c_p, c_p, c_f, c_f, c_f, c_f, c_f,
                                c_p, c_p, c_p, c_p], c_int),
+    # global-norm clip + non-finite guard (gradguard.hip): g, g_bf16, n, grad_scale, clip, guard_nonfinite,
+    # skip_in, partials, record, stream
+    "drn_grad_guard": ([c_p, c_int, c_i64, c_f, c_f, c_int, c_p, c_p, c_p, c_p], c_int),
+    "drn_grad_guard_grid": ([], c_int),
+    "drn_grad_guard_block": ([], c_int),
+    "drn_grad_guard_record_size": ([], c_int),
     "drn_lars_slot_size": ([], c_int),
     "drn_lars_chunk": ([], c_int),
     "drn_cast_bf16": ([c_p, c_p, c_i64, c_p], c_int),

@@ -14,6 +14,7 @@ Op contract (NHWC activations, KRSC conv weights, fp32 statistics):
   bn_bwd_reduce / bn_finalize_bwd / bn_bwd_apply
   pool_bnrelu, sgemm, softmax_xent(_ex, _mix), colsum, maxpool_fwd/bwd, sgd_momentum, weight_tflip
   mix_pairs(src, dst, table)                                 Mixup / CutMix of a batch with its reversal
+  grad_guard(g, grad_scale, clip, guard, skip_in, ws, rec)   global-norm clip + non-finite step guard
 where pre(x) = relu(x * scale + shift) when in_bn = (scale, shift) is given.
 """
 from __future__ import annotations
@@ -152,6 +153,28 @@ def _mix_fields(table: torch.Tensor):
     t = table.contiguous()
     f = t[:, :2].contiguous().view(torch.float32)
     return f[:, 0], f[:, 1], t[:, 2:6], t[:, 6]
+
+
+# mirror of gradguard.hip `struct GuardRecord`: the device record of grad_guard (8 words). Both
+# backends take it as an int32 [8] tensor (words 0 / 1 hold the bits of norm / scale); the optimizer's
+# skip word is record[2:3].
+GUARD_REC = np.dtype([("norm", "<f4"), ("scale", "<f4"), ("skip", "<i4"), ("skipped_total", "<i4"),
+                      ("clipped_total", "<i4"), ("steps_total", "<i4"), ("reserved", "<i4", (2,))])
+GUARD_GRID = 2048   # workgroups of both grad_guard launches = partial sums (gradguard.hip GG_GRID)
+GUARD_SKIP = 2      # word index of `skip`
+
+
+def guard_record_tensor(device="cpu") -> torch.Tensor:
+    """A zeroed grad_guard record (scale reads 1 only after the first call)."""
+    return torch.zeros(GUARD_REC.itemsize // 4, dtype=torch.int32, device=device)
+
+
+def guard_record_read(record: torch.Tensor) -> dict:
+    """The record's fields on the host (synchronizes on a device tensor)."""
+    r = record.detach().cpu().contiguous().numpy().view(GUARD_REC)[0]
+    return {"norm": float(r["norm"]), "scale": float(r["scale"]), "skip": int(r["skip"]),
+            "skipped_total": int(r["skipped_total"]), "clipped_total": int(r["clipped_total"]),
+            "steps_total": int(r["steps_total"])}
 
 
 def _aligned16(*ts):
@@ -1063,6 +1086,27 @@ class HipBackend(_Common):
                                             float(wd), float(grad_scale), float(eta), float(eps), _ptr(skip),
                                             self.stream()), "drn_lars_momentum")
 
+    def grad_guard(self, g, grad_scale, clip, guard_nonfinite, skip_in, partials, record):
+        """Global-norm clipping + the non-finite step guard of the flat gradient g (fp32 or bf16,
+        16-byte aligned) that the optimizer will scale by grad_scale (gradguard.hip; two launches):
+        norm = ||grad_scale * g||; clip > 0 and norm > clip: g *= clip / norm in place;
+        guard_nonfinite and a NaN / Inf norm, or a non-zero skip_in (optional device int32 word):
+        record.skip = 1 and g is left alone. partials: GUARD_GRID fp32 of workspace; record: a
+        guard_record_tensor on g's device, updated on the device (pass record[GUARD_SKIP:GUARD_SKIP + 1]
+        as the optimizer's skip word)."""
+        assert g.dtype in (torch.float32, torch.bfloat16) and g.is_contiguous() and g.dim() == 1
+        assert partials.dtype == torch.float32 and partials.numel() >= GUARD_GRID and partials.is_contiguous()
+        assert record.dtype == torch.int32 and record.numel() == GUARD_REC.itemsize // 4 and record.is_contiguous()
+        assert record.device == g.device == partials.device
+        assert skip_in is None or (skip_in.dtype == torch.int32 and skip_in.device == g.device)
+        if not getattr(self, "_guard_checked", False):
+            if self.L.drn_grad_guard_grid() != GUARD_GRID or self.L.drn_grad_guard_record_size() != GUARD_REC.itemsize:
+                raise _lib.KernelLibraryError("GuardRecord layout mismatch between Python and the kernel library")
+            self._guard_checked = True
+        _lib.check(self.L.drn_grad_guard(g.data_ptr(), int(g.dtype == torch.bfloat16), g.numel(), float(grad_scale),
+                                         float(clip), int(bool(guard_nonfinite)), _ptr(skip_in),
+                                         partials.data_ptr(), record.data_ptr(), self.stream()), "drn_grad_guard")
+
     def cast_bf16(self, x, y):
         _lib.check(self.L.drn_cast_bf16(x.data_ptr(), y.data_ptr(), x.numel(), self.stream()), "drn_cast_bf16")
 
@@ -1526,6 +1570,31 @@ class RefBackend(_Common):
             if ema is not None:
                 self._ema(ema[sl], ws, ema_decay_t)
             trust[i] = t
+
+    def grad_guard(self, g, grad_scale, clip, guard_nonfinite, skip_in, partials, record):
+        """HipBackend.grad_guard's contract in torch. The sum of squares is accumulated in fp64; norm
+        and scale are then fp32 values (scale = fp32 clip / max(norm, clip), as the kernel derives it
+        from the published norm) -- fp64 ones for an fp64 gradient (RefBackend(dtype=torch.float64)),
+        the record keeping their fp32 roundings. partials is not used."""
+        if not float(clip) >= 0.0:
+            raise ValueError(f"grad_guard: clip must be >= 0, got {clip!r}")
+        dt = torch.float64 if g.dtype == torch.float64 else torch.float32
+        v = (g.to(dt) * torch.tensor(float(grad_scale), dtype=dt)).double()
+        norm = torch.sqrt((v * v).sum()).to(dt)
+        finite = bool(torch.isfinite(norm))
+        c = torch.tensor(float(clip), dtype=dt)
+        scale = c / torch.maximum(norm, c) if (clip > 0 and finite) else torch.ones((), dtype=dt)
+        bad = bool(guard_nonfinite) and not finite
+        skip = bad or (skip_in is not None and int(skip_in.reshape(-1)[0]) != 0)
+        clipped = (not skip) and float(scale) != 1.0
+        f = record[:2].view(torch.float32)
+        f[0], f[1] = norm.float(), scale.float()
+        record[GUARD_SKIP] = int(skip)
+        record[3] += int(bad)
+        record[4] += int(clipped)
+        record[5] += 1
+        if clipped:
+            g.copy_((g.to(dt) * scale).to(g.dtype) if g.dtype != dt else g * scale)
 
     def cast_bf16(self, x, y):
         y.copy_(x)

@@ -106,8 +106,20 @@ class Executor:
                  weight_decay: float = 2e-4, momentum: float = 0.9, params: ParamStore | None = None,
                  materialize_bn: Optional[bool] = None, optimizer: str = "momentum", lars_eta: float = 0.001,
                  lars_eps: float = 1e-9, label_smoothing: float = 0.0, top_k: int = 0, ema_decay: float = 0.0,
-                 ema_warmup: bool = True, mix: bool = False):
+                 ema_warmup: bool = True, mix: bool = False, clip_grad_norm: float = 0.0,
+                 skip_nonfinite_grads: bool = False):
         self.spec, self.N, self.be = spec, batch, backend
+        # clip_grad_norm = c > 0: the gradient the optimizer reads is scaled by c / max(norm, c), norm
+        # its global L2 norm (grad_scale included; TF's clip_by_global_norm). skip_nonfinite_grads: a
+        # step whose norm is NaN / Inf changes no weight, momentum, bf16 copy, EMA or trust ratio.
+        # Both are decided on the device (csrc/kernels/gradguard.hip, be.grad_guard) in front of
+        # the step's single update, whose skip word is the guard's record. The norm needs every
+        # gradient, so a guarded backward never defers its tail. Both off: nothing is allocated and
+        # the step makes exactly the calls it made before
+        if not float(clip_grad_norm) >= 0.0 or float(clip_grad_norm) == float("inf"):
+            raise ValueError(f"clip_grad_norm must be a finite value >= 0, got {clip_grad_norm!r}")
+        self.clip_grad_norm, self.skip_nonfinite_grads = float(clip_grad_norm), bool(skip_nonfinite_grads)
+        self.guarding = self.clip_grad_norm > 0 or self.skip_nonfinite_grads
         # mix: the training target is mixed from two labels per sample (Mixup / CutMix): mix_table
         # holds one record per sample (ops/backend.py MIX_REC; set_mix), in device memory like the
         # LR, and the training forward's loss kernel reads lam and the second label from it
@@ -560,6 +572,13 @@ class Executor:
             self.lars_table = lars_table(self.P, self.device)
             self.lars_partials = self._f32(2 * self.lars_table.chunks)
             self.lars_trust = torch.ones(self.lars_table.n, dtype=torch.float32, device=self.device)
+        # gradient guard: the device record (norm, scale, skip word, counters) and the per-workgroup
+        # partial sums, allocated once like the LARS workspaces
+        self.guard_record = self.guard_partials = None
+        if self.guarding:
+            from ..ops.backend import GUARD_GRID, guard_record_tensor
+            self.guard_record = guard_record_tensor(self.device)
+            self.guard_partials = torch.zeros(GUARD_GRID, dtype=torch.float32, device=self.device)
 
     def _all_ops(self):
         yield self.stem_op
@@ -808,7 +827,9 @@ class Executor:
             if not (self.is_hip and torch.cuda.is_current_stream_capturing()):
                 self.sched.wait(torch.cuda.current_stream(self.device), self._tflip_ev, key="tflip")
             self._tflip_ev = None
-        deferred = defer_tail and self.side is not None and self.grad_ready is None and self._stem_hi > 0
+        # (guarding: the global norm needs every gradient before any update, so nothing is deferred)
+        deferred = defer_tail and self.side is not None and self.grad_ready is None and self._stem_hi > 0 \
+            and not self.guarding
         self._pre_ev = None
         for bp in reversed(self.blocks):
             if deferred and self.early_sgd and bp is self.blocks[0] and len(self.blocks) > 1:
@@ -1075,6 +1096,16 @@ class Executor:
         when it is non-zero at run time no parameter or momentum changes (the P2P error word)."""
         P = self.P
         g = P.grad if grad is None else grad
+        if self.guarding:
+            # join, clip / guard the buffer the optimizer is about to read (in place), one update
+            # gated by the guard's skip word (which ORs the incoming one in)
+            from ..ops.backend import GUARD_SKIP
+            self.join_grads()
+            self.be.grad_guard(g, grad_scale, self.clip_grad_norm, self.skip_nonfinite_grads, skip,
+                               self.guard_partials, self.guard_record)
+            self._update(0, P.total, g, grad_scale, self.guard_record[GUARD_SKIP:GUARD_SKIP + 1])
+            self.refresh_dgrad_weights()
+            return
         if self._tail_ev is not None and grad is None:
             # parameters [stem_hi, end) while the stem's weight gradient finishes on the side
             # stream (the stem has no data-gradient weights, so the refresh goes first too)
@@ -1105,7 +1136,19 @@ class Executor:
         if self.optimizer == "lars":
             raise RuntimeError("the sharded optimizer cuts tensors across ranks; LARS needs every tensor's whole "
                                "norm (optimizer='lars' does not support optimizer sharding)")
+        if self.guarding:
+            raise RuntimeError("a shard sees only part of the gradient; clip_grad_norm / skip_nonfinite_grads need "
+                               "its global norm (they do not support optimizer sharding)")
         self._sgd(lo, hi, self.P.grad if grad is None else grad, grad_scale)
+
+    def grad_guard_stats(self) -> Optional[dict]:
+        """The gradient guard's device record on the host (synchronizes; off the hot path): norm and
+        scale of the last guarded step, its skip word, and the skipped / clipped / guarded step
+        counts. None when neither clip_grad_norm nor skip_nonfinite_grads is on."""
+        if self.guard_record is None:
+            return None
+        from ..ops.backend import guard_record_read
+        return guard_record_read(self.guard_record)
 
     def refresh_dgrad_weights(self, stem: bool = True):
         """Rebuild the flipped / channel-transposed data-gradient weights (and the packed stem's

@@ -57,6 +57,7 @@ class LoggingHook(Hook):
         self.with_lr = with_lr
         self._t = None
         self._s = None
+        self._skipped = 0
 
     def begin(self, sess):
         self._t, self._s = time.time(), sess.global_step
@@ -82,6 +83,11 @@ class LoggingHook(Hook):
             parts.append(f"[allreduce exposed {m['comm_exposed_ms']:.2f} ms"
                          + (f", overlap {m['overlap_fraction']:.0%}" if "overlap_fraction" in m else "") + "]")
         log.info(", ".join(parts))
+        skipped = m.get("grad_skipped_steps", 0)   # (--skip_nonfinite_grads: reported once per change)
+        if skipped > self._skipped:
+            log.warning("skipped %d step(s) with non-finite gradients (%d in total): weights, momentum and EMA were "
+                        "left unchanged", skipped - self._skipped, skipped)
+            self._skipped = skipped
         if self.metrics_path:
             with open(self.metrics_path, "a") as f:
                 f.write(json.dumps({"step": step, "time": now, **m}) + "\n")
@@ -104,6 +110,10 @@ class SummaryHook(Hook):
             scalars["ema/decay"] = m["ema_decay"]
         if "mix_lam" in m:    # (--mixup_alpha / --cutmix_alpha: the batch mean of the target weight lam)
             scalars["mix/lam"] = m["mix_lam"]
+        if "grad_global_norm" in m:  # (--clip_grad_norm / --skip_nonfinite_grads: the guard's device record)
+            scalars.update({"grad/global_norm": m["grad_global_norm"], "grad/clip_scale": m["grad_clip_scale"],
+                            "grad/clipped_steps": m["grad_clipped_steps"],
+                            "grad/skipped_steps": m["grad_skipped_steps"]})
         ex = getattr(sess, "ex", None)
         if getattr(ex, "optimizer", "momentum") == "lars":
             # the last update's trust ratios of the adapting (conv / dense kernel) slots

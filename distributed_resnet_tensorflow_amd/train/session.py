@@ -80,7 +80,8 @@ class TrainingSession:
                  collective_timeout_s: float = 0.0, precision: str = "bf16", shard_optimizer: bool = False,
                  step_trial: bool = True, optimizer: str = "momentum", lars_eta: float = 0.001,
                  lars_eps: float = 1e-9, label_smoothing: float = 0.0, top_k: int = 0, ema_decay: float = 0.0,
-                 ema_warmup: bool = True, mix: bool = False):
+                 ema_warmup: bool = True, mix: bool = False, clip_grad_norm: float = 0.0,
+                 skip_nonfinite_grads: bool = False):
         self.cluster = cluster
         self.spec = spec
         self.device = torch.device(cluster.device)
@@ -88,7 +89,11 @@ class TrainingSession:
         self.ex = Executor(spec, batch, self.be, self.device, seed=seed, weight_decay=weight_decay,
                            optimizer=optimizer, lars_eta=lars_eta, lars_eps=lars_eps,
                            label_smoothing=label_smoothing, top_k=top_k, ema_decay=ema_decay,
-                           ema_warmup=ema_warmup, mix=mix)
+                           ema_warmup=ema_warmup, mix=mix, clip_grad_norm=clip_grad_norm,
+                           skip_nonfinite_grads=skip_nonfinite_grads)
+        if self.ex.guarding and shard_optimizer:
+            raise ValueError("clip_grad_norm / skip_nonfinite_grads need the gradient's global norm; a shard of the "
+                             "sharded optimizer sees only part of it")
         self.lr = lr_schedule
         self.meta = meta or {}
         # DRN_FORCE_DP=1: the data-parallel engine on a single-rank process group (profiling the
@@ -469,6 +474,12 @@ class TrainingSession:
             if self.ex.mix_table is not None:
                 # the batch mean of lam of the last step's mix table (column 1 holds lam's bits)
                 m["mix_lam"] = float(self.ex.mix_table[:, 1].contiguous().view(torch.float32).double().mean())
+            gs = self.ex.grad_guard_stats()
+            if gs is not None:
+                # the last step's global gradient norm and clip factor, and the running counts of
+                # clipped / skipped (non-finite) steps, from the guard's device record
+                m.update({"grad_global_norm": gs["norm"], "grad_clip_scale": gs["scale"],
+                          "grad_clipped_steps": gs["clipped_total"], "grad_skipped_steps": gs["skipped_total"]})
             if self.engine is not None:
                 m.update(self.engine.stats())
                 self._guard(self.engine.check_errors)

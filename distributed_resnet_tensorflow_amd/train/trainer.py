@@ -55,7 +55,8 @@ def _meta(FLAGS, spec):
             "spec_name": spec.name,
             "optimizer": FLAGS.optimizer, "eta": FLAGS.lars_eta, "eps": FLAGS.lars_eps,
             "label_smoothing": FLAGS.label_smoothing, "ema_decay": FLAGS.ema_decay,
-            "mixup_alpha": FLAGS.mixup_alpha, "cutmix_alpha": FLAGS.cutmix_alpha}
+            "mixup_alpha": FLAGS.mixup_alpha, "cutmix_alpha": FLAGS.cutmix_alpha,
+            "clip_grad_norm": FLAGS.clip_grad_norm, "skip_nonfinite_grads": FLAGS.skip_nonfinite_grads}
 
 
 def mixing(FLAGS) -> bool:
@@ -133,7 +134,8 @@ def train(FLAGS, cluster=None):
                            shard_optimizer=FLAGS.optimizer_sharding, optimizer=FLAGS.optimizer,
                            lars_eta=FLAGS.lars_eta, lars_eps=FLAGS.lars_eps,
                            label_smoothing=FLAGS.label_smoothing, top_k=FLAGS.top_k, ema_decay=FLAGS.ema_decay,
-                           ema_warmup=FLAGS.ema_warmup, mix=mixing(FLAGS))
+                           ema_warmup=FLAGS.ema_warmup, mix=mixing(FLAGS), clip_grad_norm=FLAGS.clip_grad_norm,
+                           skip_nonfinite_grads=FLAGS.skip_nonfinite_grads)
     feeder = make_feeder(FLAGS, sess.ex, cluster, True, sess.data_state)
     is_imagenet = FLAGS.dataset == "imagenet"
     hooks = [LoggingHook(FLAGS.log_every_n_steps, FLAGS.batch_size * cluster.world,
