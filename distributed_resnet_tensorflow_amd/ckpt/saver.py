@@ -182,4 +182,8 @@ class Saver:
         meta["skip_nonfinite_grads"] = bool(meta.get("skip_nonfinite_grads", False))
         meta["mixup_alpha"] = float(meta.get("mixup_alpha", 0.0))
         meta["cutmix_alpha"] = float(meta.get("cutmix_alpha", 0.0))
+        # the ImageNet input pipeline: absent = the reference's VGG pipeline and the flag defaults
+        meta["imagenet_preprocessing"] = str(meta.get("imagenet_preprocessing", "vgg"))
+        meta["rrc_scale_min"] = float(meta.get("rrc_scale_min", 0.08))
+        meta["color_jitter"] = float(meta.get("color_jitter", 0.0))
         return meta

@@ -14,6 +14,11 @@ Host side: TFRecord scan (native CRC check), Example parsing, JPEG decode (PIL, 
 and the per-image geometry draws. GPU side: one fused resize+crop+flip+mean-sub kernel over
 the packed decoded batch (csrc/kernels/augment.hip, drn_vgg_preprocess); the CPU path runs the
 same math in numpy (RefBackend.vgg_preprocess).
+
+preprocessing="inception" (not in the reference): random-resized crop, flip, colour jitter and mean / std
+normalisation; the host draws one BOX_DESC record per image, csrc/kernels/input_box.hip
+(drn_box_preprocess) resamples the box with the anti-aliased triangle filter, and box_preprocess_np below
+is the fp64 reference that RefBackend.box_preprocess runs.
 """
 from __future__ import annotations
 
@@ -157,6 +162,161 @@ def vgg_preprocess_np(img: np.ndarray, rh: int, rw: int, cy: int, cx: int, flip:
     return res - np.array(RGB_MEANS, dtype=np.float32)
 
 
+# -- Inception-style input: random-resized crop, colour jitter, mean / std -----------------------------
+# (--imagenet_preprocessing=inception; GPU: csrc/kernels/input_box.hip, CPU: RefBackend.box_preprocess
+# runs the fp64 reference below.) All arithmetic is on [0, 1] pixels.
+PREPROCESSINGS = ("vgg", "inception")
+NORM_MEAN = (0.485, 0.456, 0.406)
+NORM_STD = (0.229, 0.224, 0.225)
+RRC_SCALE_MIN = 0.08
+RRC_RATIO = (3.0 / 4.0, 4.0 / 3.0)
+RRC_TRIES = 10
+EVAL_CROP_FRACTION = 224.0 / 256.0
+GRAY = (0.299, 0.587, 0.114)
+OP_BRIGHTNESS, OP_CONTRAST, OP_SATURATION = 0, 1, 2
+COLOR_ORDERS = ((0, 1, 2), (0, 2, 1), (1, 0, 2), (1, 2, 0), (2, 0, 1), (2, 1, 0))
+
+# numpy mirror of csrc/kernels/input_box.hip `struct BoxDesc` (64 bytes)
+BOX_DESC = np.dtype([("offset", "<i8"), ("H", "<i4"), ("W", "<i4"), ("by", "<i4"), ("bx", "<i4"), ("bh", "<i4"),
+                     ("bw", "<i4"), ("flip", "<i4"), ("order", "<i4"), ("ab", "<f4"), ("ac", "<f4"), ("as", "<f4"),
+                     ("pad", "<i4", (3,))])
+assert BOX_DESC.itemsize == 64
+
+
+def desc_dtype(preprocessing: str) -> np.dtype:
+    if preprocessing not in PREPROCESSINGS:
+        raise ValueError(f"imagenet preprocessing must be one of {PREPROCESSINGS}, got {preprocessing!r}")
+    return BOX_DESC if preprocessing == "inception" else IMG_DESC
+
+
+def pack_order(ops) -> int:
+    """The three colour operations, first to last, as BoxDesc.order (2 bits each)."""
+    assert sorted(ops) == [0, 1, 2], ops
+    return int(ops[0]) | int(ops[1]) << 2 | int(ops[2]) << 4
+
+
+def unpack_order(order: int):
+    return tuple((int(order) >> (2 * k)) & 3 for k in range(3))
+
+
+ORDER_IDENTITY = pack_order((0, 1, 2))
+
+
+def draw_box(h: int, w: int, is_training: bool, rng: np.random.Generator, scale_min: float = RRC_SCALE_MIN):
+    """(by, bx, bh, bw, flip). Training: torchvision's RandomResizedCrop.get_params (area H W U(scale_min, 1),
+    log-uniform ratio in [3/4, 4/3], 10 tries, then the central crop clamped to the ratio bounds) and a
+    Bernoulli(1/2) flip. Evaluation: the central square of side round(0.875 min(H, W)), no flip."""
+    if not is_training:
+        side = max(1, int(round(min(h, w) * EVAL_CROP_FRACTION)))
+        return (h - side) // 2, (w - side) // 2, side, side, 0
+    area = h * w
+    lo, hi = np.log(RRC_RATIO[0]), np.log(RRC_RATIO[1])
+    box = None
+    for _ in range(RRC_TRIES):
+        target = area * rng.uniform(scale_min, 1.0)
+        ratio = np.exp(rng.uniform(lo, hi))
+        bw, bh = int(round(np.sqrt(target * ratio))), int(round(np.sqrt(target / ratio)))
+        if 0 < bw <= w and 0 < bh <= h:
+            box = (int(rng.integers(0, h - bh + 1)), int(rng.integers(0, w - bw + 1)), bh, bw)
+            break
+    if box is None:
+        in_ratio = w / h
+        if in_ratio < RRC_RATIO[0]:
+            bw, bh = w, min(h, int(round(w / RRC_RATIO[0])))
+        elif in_ratio > RRC_RATIO[1]:
+            bh, bw = h, min(w, int(round(h * RRC_RATIO[1])))
+        else:
+            bh, bw = h, w
+        box = ((h - bh) // 2, (w - bw) // 2, bh, bw)
+    return box + (int(rng.integers(0, 2)),)
+
+
+def draw_jitter(jitter: float, rng: np.random.Generator):
+    """(order, a_b, a_c, a_s): the factors from U[1 - j, 1 + j] and a uniformly drawn order of the three
+    operations; the identity without drawing anything when j == 0."""
+    if not jitter > 0:
+        return ORDER_IDENTITY, 1.0, 1.0, 1.0
+    ab, ac, asat = (float(np.float32(rng.uniform(1.0 - jitter, 1.0 + jitter))) for _ in range(3))
+    return pack_order(COLOR_ORDERS[int(rng.integers(0, len(COLOR_ORDERS)))]), ab, ac, asat
+
+
+def aa_taps(box_len: int, out_len: int, i: int):
+    """Tap range [lo, hi) of output i, in exact integer arithmetic: lo = max(0, int(c - support + 0.5)),
+    hi = min(box_len, int(c + support + 0.5)) with scale = box_len / out_len, support = max(scale, 1),
+    c = scale (i + 0.5), all over the common denominator 2 out_len."""
+    L, O = int(box_len), int(out_len)
+    if L >= O:
+        lo, hi = L * (2 * i - 1) + O, L * (2 * i + 3) + O
+    else:
+        lo, hi = L * (2 * i + 1) - O, L * (2 * i + 1) + 3 * O
+    return max(0, lo // (2 * O)), min(L, hi // (2 * O))
+
+
+def aa_weights(box_len: int, out_len: int) -> np.ndarray:
+    """[out_len, box_len] fp64 matrix of the anti-aliased triangle filter (rows sum to 1):
+    w = max(0, 1 - |(j - c + 0.5) / max(scale, 1)|) over aa_taps."""
+    L, O = int(box_len), int(out_len)
+    scale = L / O
+    inv = 1.0 / max(scale, 1.0)
+    m = np.zeros((O, L), dtype=np.float64)
+    for i in range(O):
+        lo, hi = aa_taps(L, O, i)
+        j = np.arange(lo, hi, dtype=np.float64)
+        w = np.maximum(0.0, 1.0 - np.abs((j - scale * (i + 0.5) + 0.5) * inv))
+        m[i, lo:hi] = w / w.sum()
+    return m
+
+
+def box_resample_np(img: np.ndarray, by: int, bx: int, bh: int, bw: int, oh: int, ow: int) -> np.ndarray:
+    """Crop the box, then resample it to oh x ow with the separable anti-aliased triangle filter (torch's
+    interpolate(bilinear, align_corners=False, antialias=True) on the crop). fp64 [oh, ow, C], the input's scale."""
+    H, W = img.shape[:2]
+    if not (0 <= by and 0 <= bx and bh > 0 and bw > 0 and by + bh <= H and bx + bw <= W):
+        raise ValueError(f"box {(by, bx, bh, bw)} does not lie inside the {H} x {W} image")
+    crop = img[by:by + bh, bx:bx + bw].astype(np.float64)
+    rows = np.einsum("ij,jkc->ikc", aa_weights(bw, ow), crop.transpose(1, 0, 2))   # [ow, bh, C]
+    return np.einsum("ij,jkc->ikc", aa_weights(bh, oh), rows.transpose(1, 0, 2))    # [oh, ow, C]
+
+
+def gray_np(x: np.ndarray) -> np.ndarray:
+    return x[..., 0] * GRAY[0] + x[..., 1] * GRAY[1] + x[..., 2] * GRAY[2]
+
+
+def contrast_mean(m0: float, ops, ab: float) -> float:
+    """The mean gray the contrast operation sees: nothing is clamped, so brightness scales the mean gray
+    by a_b and saturation and contrast keep it: m = m0 * (a_b if brightness precedes contrast else 1)."""
+    ops = tuple(ops)
+    return m0 * (ab if ops.index(OP_BRIGHTNESS) < ops.index(OP_CONTRAST) else 1.0)
+
+
+def color_jitter_np(x: np.ndarray, order: int, ab: float, ac: float, asat: float) -> np.ndarray:
+    """The three unclamped colour operations (the fb.resnet.torch form) on fp64 [H, W, 3] pixels."""
+    ops = unpack_order(order)
+    m = contrast_mean(float(gray_np(x).mean()), ops, ab)
+    x = np.array(x, dtype=np.float64)
+    for op in ops:
+        if op == OP_BRIGHTNESS:
+            x = ab * x
+        elif op == OP_CONTRAST:
+            x = ac * x + (1.0 - ac) * m
+        else:
+            x = asat * x + (1.0 - asat) * gray_np(x)[..., None]
+    return x
+
+
+def box_preprocess_np(img: np.ndarray, d, oh: int = IMAGE_SIZE, ow: int = IMAGE_SIZE, jitter: bool = True,
+                      mean=NORM_MEAN, std=NORM_STD) -> np.ndarray:
+    """fp64 reference of the Inception-style input for one image and its BOX_DESC record d: box resample on
+    [0, 1] pixels, colour jitter (jitter=False ignores the record's factors), flip of the output columns,
+    (x - mean) / std. Returns float64 [oh, ow, 3]."""
+    x = box_resample_np(img, int(d["by"]), int(d["bx"]), int(d["bh"]), int(d["bw"]), oh, ow) / 255.0
+    if jitter:
+        x = color_jitter_np(x, int(d["order"]), float(d["ab"]), float(d["ac"]), float(d["as"]))
+    if int(d["flip"]):
+        x = x[:, ::-1]
+    return (x - np.asarray(mean, dtype=np.float64)) / np.asarray(std, dtype=np.float64)
+
+
 class _Shard:
     """Record index of one TFRecord shard: the file is memory-mapped and only the 12-byte
     record headers are walked (no payload read, no CRC) when the index is built; each record's
@@ -293,7 +453,9 @@ class _ShmImage:
 
 class ImagenetLoader:
     """Background pipeline producing packed decoded batches:
-    (packed uint8 buffer, IMG_DESC array [B], int32 labels [B]).
+    (packed uint8 buffer, IMG_DESC array [B], int32 labels [B]); with preprocessing="inception" the
+    descriptors are BOX_DESC records (random-resized crop boxes with area fraction U(scale_min, 1), flips
+    and, for color_jitter > 0, the colour factors and operation order), drawn from the same per-batch RNG.
 
     The record order is a pure function of (seed, rank, epoch): per-epoch file shuffle, then the
     reference's 1500-deep example shuffle buffer (resnet_imagenet_main.py:165-173) run over
@@ -313,7 +475,17 @@ class ImagenetLoader:
     def __init__(self, data_dir: str, batch_size: int, is_training: bool, seed: int = 0, rank: int = 0,
                  world: int = 1, num_threads: int = 8, prefetch: int = 3, num_epochs: Optional[int] = None,
                  epoch: int = 0, cursor: int = 0, batch_index: int = 0, pin: bool = False, pin_device=None,
-                 workers: str = "thread"):
+                 workers: str = "thread", preprocessing: str = "vgg", scale_min: float = RRC_SCALE_MIN,
+                 color_jitter: float = 0.0):
+        self.preprocessing, self.desc_dtype = preprocessing, desc_dtype(preprocessing)
+        if not 0.0 < scale_min <= 1.0:
+            raise ValueError(f"scale_min must be in (0, 1], got {scale_min!r}")
+        if not 0.0 <= color_jitter < 1.0:
+            raise ValueError(f"color_jitter must be in [0, 1), got {color_jitter!r}")
+        if color_jitter > 0 and preprocessing != "inception":
+            raise ValueError("color_jitter needs preprocessing='inception'")
+        # (evaluation never jitters)
+        self.scale_min, self.color_jitter = float(scale_min), float(color_jitter) if is_training else 0.0
         files = filenames(is_training, data_dir)
         if is_training and world > 1:
             files = files[rank::world] or files
@@ -437,15 +609,20 @@ class ImagenetLoader:
                 rng = np.random.default_rng([self.seed, self.rank, 99, b])
                 total = sum(d[0].size for d in decoded)
                 packed, flat = self._host(total, np.uint8)
-                desc_h, desc = self._host(self.bs, IMG_DESC)
+                desc_h, desc = self._host(self.bs, self.desc_dtype)
                 labels_h, labels = self._host(self.bs, np.int32)
-                desc[...] = np.zeros((), dtype=IMG_DESC)
+                desc[...] = np.zeros((), dtype=self.desc_dtype)
                 off = 0
                 for i, (img, lab) in enumerate(decoded):
                     h, w = img.shape[:2]
                     flat[off:off + img.size] = img.reshape(-1)
-                    rh, rw, cy, cx, flip = draw_geometry(h, w, self.train, rng)
-                    desc[i] = (off, h, w, rh, rw, cy, cx, flip, 0)
+                    if self.preprocessing == "inception":
+                        by, bx, bh, bw, flip = draw_box(h, w, self.train, rng, self.scale_min)
+                        order, ab, ac, asat = draw_jitter(self.color_jitter, rng)
+                        desc[i] = (off, h, w, by, bx, bh, bw, flip, order, ab, ac, asat, (0, 0, 0))
+                    else:
+                        rh, rw, cy, cx, flip = draw_geometry(h, w, self.train, rng)
+                        desc[i] = (off, h, w, rh, rw, cy, cx, flip, 0)
                     labels[i] = lab
                     off += img.size
                 decoded = None

@@ -185,6 +185,20 @@ def validate(fv: "FlagValues") -> None:
                              "global norm")
         if fv.model == "lrnet":
             raise FlagsError("--clip_grad_norm / --skip_nonfinite_grads are not supported by --model=lrnet")
+    if fv.imagenet_preprocessing not in ("vgg", "inception"):
+        raise FlagsError(f"--imagenet_preprocessing must be vgg or inception, got {fv.imagenet_preprocessing!r}")
+    if not 0.0 < fv.rrc_scale_min <= 1.0:
+        raise FlagsError(f"--rrc_scale_min must be in (0, 1], got {fv.rrc_scale_min!r}")
+    if not 0.0 <= fv.color_jitter < 1.0:
+        raise FlagsError(f"--color_jitter must be in [0, 1), got {fv.color_jitter!r}")
+    if fv.imagenet_preprocessing == "inception" or fv.color_jitter > 0:
+        if fv.dataset in ("cifar10", "cifar100"):
+            raise FlagsError("--imagenet_preprocessing=inception / --color_jitter are ImageNet input options: "
+                             f"not supported with --dataset={fv.dataset}")
+        if fv.model == "lrnet":
+            raise FlagsError("--imagenet_preprocessing=inception / --color_jitter are not supported by --model=lrnet")
+    if fv.color_jitter > 0 and fv.imagenet_preprocessing != "inception":
+        raise FlagsError("--color_jitter > 0 needs --imagenet_preprocessing=inception")
 
 
 FLAGS = FlagValues()
@@ -304,6 +318,15 @@ def define_reference_flags(flag_values: FlagValues = FLAGS, **defaults) -> FlagV
     B("skip_nonfinite_grads", False, "Skip the update of a step whose gradient holds a NaN or Inf (global norm not "
       "finite): weights, momentum, EMA and LARS trust ratios stay as they were; global_step and the LR schedule "
       "still advance, BatchNorm moving statistics keep the step's update.", fv)
+    S("imagenet_preprocessing", "vgg", "vgg (the reference's pipeline: aspect-preserving resize to U{256..512}, random "
+      "224 crop, flip, mean subtraction) or inception (random-resized crop with the anti-aliased triangle filter, "
+      "flip, optional --color_jitter, mean / std normalisation; evaluation: the 0.875 central crop). The evaluators "
+      "take it from the checkpoint's .meta.", fv)
+    Fl("rrc_scale_min", 0.08, "--imagenet_preprocessing=inception: the random-resized crop's area is U(v, 1) of the "
+       "image's (0 < v <= 1).", fv)
+    Fl("color_jitter", 0.0, "j > 0 (needs --imagenet_preprocessing=inception): brightness, contrast and saturation "
+       "factors from U[1 - j, 1 + j], applied unclamped in a random order per training image (0 <= j < 1). 0 = off.",
+       fv)
     I("collective_timeout_secs", 600,"Process-group timeout and collective-watchdog limit: a rank whose "
       "gradient exchange stalls this long exits (the launcher restarts the job from its checkpoint).", fv)
     I("fault_inject_step", -1, "Kill this process at the given global step (fault-injection tests).", fv)

@@ -151,6 +151,13 @@ _SIGS = {
     "drn_fill_f32": ([c_p, c_i64, c_f, c_p], c_int),
     "drn_cifar_augment": ([c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_p], c_int),
     "drn_vgg_preprocess": ([c_p, c_p, c_p, c_int, c_int, c_int, c_f, c_f, c_f, c_p], c_int),
+    # Inception-style input (input_box.hip): in, nbytes, desc, out, [scratch, partial,] N, OH, OW, mean x 3,
+    # std x 3, force_direct, stream
+    "drn_box_preprocess": ([c_p, c_i64, c_p, c_p, c_int, c_int, c_int] + [c_f] * 6 + [c_int, c_p], c_int),
+    "drn_box_preprocess_jitter": ([c_p, c_i64, c_p, c_p, c_p, c_p, c_int, c_int, c_int] + [c_f] * 6 + [c_int, c_p],
+                                  c_int),
+    "drn_box_tiles": ([c_int, c_int], c_int),
+    "drn_box_desc_size": ([], c_int),
     "drn_p2p_signal": ([c_p, c_int, c_p], c_int),
     "drn_p2p_reduce": ([c_p, c_int, c_int, c_p], c_int),
     "drn_p2p_reduce2": ([c_p, c_int, c_int, c_p], c_int),

@@ -14,6 +14,7 @@ Op contract (NHWC activations, KRSC conv weights, fp32 statistics):
   bn_bwd_reduce / bn_finalize_bwd / bn_bwd_apply
   pool_bnrelu, sgemm, softmax_xent(_ex, _mix), colsum, maxpool_fwd/bwd, sgd_momentum, weight_tflip
   mix_pairs(src, dst, table)                                 Mixup / CutMix of a batch with its reversal
+  box_preprocess(packed, desc, out, mean, std, jitter)       Inception-style input: box resample, colour jitter
   grad_guard(g, grad_scale, clip, guard, skip_in, ws, rec)   global-norm clip + non-finite step guard
 where pre(x) = relu(x * scale + shift) when in_bn = (scale, shift) is given.
 """
@@ -1173,6 +1174,33 @@ class HipBackend(_Common):
                                              float(means[0]), float(means[1]), float(means[2]), self.stream()),
                    "drn_vgg_preprocess")
 
+    def box_preprocess(self, packed_u8, desc, out, mean, std, jitter=False, force_direct=False):
+        """Inception-style input (csrc/kernels/input_box.hip): packed decoded uint8 batch + N BOX_DESC
+        records (raw bytes, on the device) -> out [N, OH, OW, 8] bf16, the box of every image resampled
+        with the anti-aliased triangle filter, flipped and normalised with mean / std. jitter=True also
+        applies the records' colour factors (a second launch over an fp32 copy kept by the backend);
+        force_direct takes the direct-tap path for every tile (tests)."""
+        N, OH, OW, C = out.shape
+        assert C == 8 and out.dtype == torch.bfloat16 and out.is_contiguous(), "box_preprocess: out is NHWC8 bf16"
+        assert packed_u8.dtype == torch.uint8 and packed_u8.is_contiguous()
+        assert desc.numel() * desc.element_size() >= N * 64, "box_preprocess: desc holds N 64-byte records"
+        ms = [float(v) for v in tuple(mean) + tuple(std)]
+        if not jitter:
+            _lib.check(self.L.drn_box_preprocess(packed_u8.data_ptr(), packed_u8.numel(), desc.data_ptr(),
+                                                 out.data_ptr(), N, OH, OW, *ms, int(force_direct), self.stream()),
+                       "drn_box_preprocess")
+            return
+        key = (N, OH, OW, out.device)
+        ws = getattr(self, "_box_ws", None)
+        if ws is None or ws[0] != key:
+            ws = (key, torch.empty(N * OH * OW, 4, dtype=torch.float32, device=out.device),
+                  torch.empty(N * self.L.drn_box_tiles(OH, OW), dtype=torch.float32, device=out.device))
+            self._box_ws = ws
+        _lib.check(self.L.drn_box_preprocess_jitter(packed_u8.data_ptr(), packed_u8.numel(), desc.data_ptr(),
+                                                    out.data_ptr(), ws[1].data_ptr(), ws[2].data_ptr(), N, OH, OW,
+                                                    *ms, int(force_direct), self.stream()),
+                   "drn_box_preprocess_jitter")
+
     def synthetic_images(self, out, seed):
         N, H, W, C = out.shape
         assert C == 8
@@ -1640,6 +1668,23 @@ class RefBackend(_Common):
             img = buf[int(r["offset"]):int(r["offset"]) + int(r["H"]) * int(r["W"]) * 3].reshape(int(r["H"]), int(r["W"]), 3)
             res[i, :, :, :3] = torch.from_numpy(vgg_preprocess_np(img, int(r["rh"]), int(r["rw"]), int(r["cy"]),
                                                                   int(r["cx"]), int(r["flip"]), OH))
+        out.copy_(res)
+
+    def box_preprocess(self, packed_u8, desc, out, mean, std, jitter=False, force_direct=False):
+        """HipBackend.box_preprocess's contract: data.imagenet.box_preprocess_np (fp64) per image."""
+        from ..data.imagenet import BOX_DESC, box_preprocess_np
+        N, OH, OW, _ = out.shape
+        d = desc if isinstance(desc, np.ndarray) else desc.cpu().numpy()
+        d = d.view(BOX_DESC).reshape(-1) if d.dtype != BOX_DESC else d
+        buf = packed_u8.cpu().numpy() if hasattr(packed_u8, "cpu") else packed_u8
+        res = torch.zeros(N, OH, OW, out.shape[-1], dtype=_DT[0])
+        for i in range(N):
+            r = d[i]
+            off, H, W = int(r["offset"]), int(r["H"]), int(r["W"])
+            if off < 0 or off + H * W * 3 > buf.size:
+                raise ValueError(f"box_preprocess: image {i} does not lie inside the packed buffer")
+            img = buf[off:off + H * W * 3].reshape(H, W, 3)
+            res[i, :, :, :3] = torch.from_numpy(box_preprocess_np(img, r, OH, OW, jitter, mean, std)).to(_DT[0])
         out.copy_(res)
 
     def synthetic_images(self, out, seed):

@@ -7,6 +7,7 @@ precision is accumulated beside it (`precision@K` in the log, `Precision@K` / `B
 summaries, `precision_top_k` in the results and in best_precision.json); "best" stays top-1.
 With --eval_ema the checkpoint's `<var>/ExponentialMovingAverage` tensors (training with
 --ema_decay) are evaluated in place of the variables; best_precision.json then records "ema": true.
+The ImageNet input pipeline (vgg or inception) is the one the checkpoint's .meta records.
 
 Fixes of reference quirks: no busy-spin when there is no checkpoint (Q8), best precision
 persisted in eval_dir/best_precision.json across restarts (Q11), the eval set is read in order
@@ -22,6 +23,7 @@ import time
 import torch
 
 from ..ckpt.saver import Saver, latest_checkpoint, step_of
+from ..flags import FlagsError
 from ..parallel import cluster as cl
 from ..runtime.executor import Executor
 from ..runtime.state import NoEmaInCheckpoint, has_ema, import_state
@@ -37,6 +39,19 @@ def _load_best(path, key="best_precision"):
         return float(json.load(open(path))[key])
     except Exception:
         return 0.0
+
+
+def checkpoint_preprocessing(FLAGS, prefix: str) -> str:
+    """The ImageNet input pipeline the checkpoint was trained with (its .meta; absent = vgg), so that
+    evaluation normalises the way training did. An explicit --imagenet_preprocessing that contradicts
+    the .meta is an error."""
+    was = Saver.restore_meta(prefix)["imagenet_preprocessing"]
+    if "imagenet_preprocessing" in FLAGS and FLAGS.is_present("imagenet_preprocessing") \
+            and FLAGS.imagenet_preprocessing != was:
+        raise FlagsError(f"--imagenet_preprocessing={FLAGS.imagenet_preprocessing} contradicts checkpoint {prefix}, "
+                         f"whose .meta records imagenet_preprocessing={was}: evaluation must normalise its input "
+                         "the way training did (drop the flag; the evaluator reads it from the .meta)")
+    return was
 
 
 def evaluate(FLAGS, eval_batch_size: int = 100, max_evals: int = -1):
@@ -81,7 +96,8 @@ def evaluate(FLAGS, eval_batch_size: int = 100, max_evals: int = -1):
             if prefix is not None:
                 last = prefix
                 step = ex.P.global_step or step_of(prefix)
-                feeder = make_feeder(FLAGS, ex, cluster, False, batch=eval_batch_size)
+                feeder = make_feeder(FLAGS, ex, cluster, False, batch=eval_batch_size,
+                                     preprocessing=checkpoint_preprocessing(FLAGS, prefix))
                 total_loss, correct, correct_k, total = 0.0, 0, 0, 0
                 try:
                     for _ in range(FLAGS.eval_batch_count):

@@ -2,7 +2,8 @@
 
 GPU path: host batch -> pinned staging tensors -> async H2D copy on a side stream (overlaps the
 previous step's compute) -> GPU preprocessing kernel (CIFAR crop/flip/standardize, or the
-fused VGG resize/crop/flip/mean-sub) writing NHWC bf16 (C padded to 8) straight into
+fused VGG resize/crop/flip/mean-sub, or the Inception-style box resample / colour jitter / mean-std
+of a loader made with preprocessing="inception") writing NHWC bf16 (C padded to 8) straight into
 `executor.images`. CPU path: the reference backend runs the same preprocessing in fp32.
 Synthetic mode fills the device batch once (benchmarks: BASELINE "synthetic data").
 
@@ -241,7 +242,11 @@ class ImagenetFeeder(_StagedFeeder):
         self.inet = inet
         self.loader = loader
         self.d_buf = torch.empty(max_bytes, dtype=torch.uint8, device=ex.device)
-        self.d_desc = torch.empty(ex.N * inet.IMG_DESC.itemsize, dtype=torch.uint8, device=ex.device)
+        # the loader decides the pipeline: IMG_DESC records (vgg) or BOX_DESC records (inception)
+        self.preprocessing = getattr(loader, "preprocessing", "vgg")
+        self.desc_dtype = inet.desc_dtype(self.preprocessing)
+        self.jitter = float(getattr(loader, "color_jitter", 0.0)) > 0
+        self.d_desc = torch.empty(ex.N * self.desc_dtype.itemsize, dtype=torch.uint8, device=ex.device)
         self.d_lab = torch.empty(ex.N, dtype=torch.int32, device=ex.device)
         self.h_packed = None  # CPU path: the reference backend preprocesses from host memory
         self.h_desc = None
@@ -255,7 +260,7 @@ class ImagenetFeeder(_StagedFeeder):
         desc_bytes = desc if isinstance(desc, torch.Tensor) else desc.view(np.uint8)
         if not self.gpu:
             self.h_packed = packed
-            self.h_desc = desc.numpy().view(self.inet.IMG_DESC) if isinstance(desc, torch.Tensor) else desc
+            self.h_desc = desc.numpy().view(self.desc_dtype) if isinstance(desc, torch.Tensor) else desc
             self.d_lab.copy_(_as_tensor(labels))
             self._stage(self._mix_pairs(labels))
             return
@@ -278,9 +283,11 @@ class ImagenetFeeder(_StagedFeeder):
                     + self._mix_pairs(labels))
 
     def _consume(self):
-        if self.gpu:
-            self.ex.be.vgg_preprocess(self.d_buf, self.d_desc, self.ex.images, self.inet.RGB_MEANS)
+        packed, desc = (self.d_buf, self.d_desc) if self.gpu else (self.h_packed, self.h_desc)
+        if self.preprocessing == "inception":
+            self.ex.be.box_preprocess(packed, desc, self.ex.images, self.inet.NORM_MEAN, self.inet.NORM_STD,
+                                      jitter=self.jitter)
         else:
-            self.ex.be.vgg_preprocess(self.h_packed, self.h_desc, self.ex.images, self.inet.RGB_MEANS)
+            self.ex.be.vgg_preprocess(packed, desc, self.ex.images, self.inet.RGB_MEANS)
         self.ex.labels.copy_(self.d_lab)
         self._mix_consume()

@@ -56,7 +56,9 @@ def _meta(FLAGS, spec):
             "optimizer": FLAGS.optimizer, "eta": FLAGS.lars_eta, "eps": FLAGS.lars_eps,
             "label_smoothing": FLAGS.label_smoothing, "ema_decay": FLAGS.ema_decay,
             "mixup_alpha": FLAGS.mixup_alpha, "cutmix_alpha": FLAGS.cutmix_alpha,
-            "clip_grad_norm": FLAGS.clip_grad_norm, "skip_nonfinite_grads": FLAGS.skip_nonfinite_grads}
+            "clip_grad_norm": FLAGS.clip_grad_norm, "skip_nonfinite_grads": FLAGS.skip_nonfinite_grads,
+            "imagenet_preprocessing": FLAGS.imagenet_preprocessing, "rrc_scale_min": FLAGS.rrc_scale_min,
+            "color_jitter": FLAGS.color_jitter}
 
 
 def mixing(FLAGS) -> bool:
@@ -76,7 +78,9 @@ def make_mix_sampler(FLAGS, ex, cluster):
                       seed=FLAGS.seed, rank=cluster.rank)
 
 
-def make_feeder(FLAGS, ex, cluster, is_training: bool, data_state=None, batch=None):
+def make_feeder(FLAGS, ex, cluster, is_training: bool, data_state=None, batch=None, preprocessing=None):
+    """preprocessing: the ImageNet input pipeline in place of --imagenet_preprocessing (the evaluators pass
+    what the checkpoint's .meta records)."""
     bs = batch or ex.N
     ds = data_state or {}
     # (training feeders only: evaluation never mixes)
@@ -99,7 +103,10 @@ def make_feeder(FLAGS, ex, cluster, is_training: bool, data_state=None, batch=No
                                      num_threads=max(2, FLAGS.num_workers * 4),
                                      num_epochs=FLAGS.num_epochs if is_training else 1,
                                      epoch=int(ds.get("data_epoch", 0)), cursor=int(ds.get("data_cursor", 0)),
-                                     batch_index=int(ds.get("data_batch", 0)), workers=FLAGS.input_workers, **pin)
+                                     batch_index=int(ds.get("data_batch", 0)), workers=FLAGS.input_workers,
+                                     preprocessing=preprocessing or FLAGS.imagenet_preprocessing,
+                                     scale_min=FLAGS.rrc_scale_min,
+                                     color_jitter=FLAGS.color_jitter if is_training else 0.0, **pin)
     return ImagenetFeeder(ex, loader, is_training, **mix)
 
 
