@@ -24,6 +24,28 @@ __device__ __forceinline__ float4 grad4(const bf16_t* g, int64_t i) {
 __device__ __forceinline__ float grad1(const float* g, int64_t i) { return g[i]; }
 __device__ __forceinline__ float grad1(const bf16_t* g, int64_t i) { return bf2f(g[i]); }
 
+// Element updates g' -> m -> w of a float4, and of one element for the tail of a LARS slot. The two
+// differ on purpose (what the compiler may contract into FMAs);
+// test_lars_with_unit_trust_is_the_momentum_kernel pins that trust == 1 gives the momentum bits.
+struct MomentumUpd {
+  float lr, mu, wd, grad_scale;
+  __device__ __forceinline__ void operator()(float& wv, float& mv, float gv) const {
+    const float gg = gv * grad_scale + wd * wv; mv = mu * mv + gg; wv -= lr * mv;
+  }
+};
+struct LarsUpd {
+  float lr, mu, wd, grad_scale, trust;
+  __device__ __forceinline__ void operator()(float& wv, float& mv, float gv) const {
+    const float gg = trust * (gv * grad_scale + wd * wv);
+    mv = __builtin_fmaf(mu, mv, gg);
+    wv -= lr * mv;
+  }
+};
+template <typename U>
+__device__ __forceinline__ void upd4(const U& upd, float4& wv, float4& mv, const float4& gv) {
+  upd(wv.x, mv.x, gv.x); upd(wv.y, mv.y, gv.y); upd(wv.z, mv.z, gv.z); upd(wv.w, mv.w, gv.w);
+}
+
 template <typename G>
 __global__ __launch_bounds__(256) void sgd_momentum_kernel(float* __restrict__ w, float* __restrict__ m,
                                                            const G* __restrict__ g, bf16_t* __restrict__ wb,
@@ -32,13 +54,7 @@ __global__ __launch_bounds__(256) void sgd_momentum_kernel(float* __restrict__ w
   // skip: the step's gradient exchange failed (P2P error word): apply no update at all
   if (skip != nullptr && *skip != 0) return;
   const float lr = *lr_ptr;
-  auto upd = [&](float4& wv, float4& mv, const float4& gv) {
-    float gg;
-    gg = gv.x * grad_scale + wd * wv.x; mv.x = mu * mv.x + gg; wv.x -= lr * mv.x;
-    gg = gv.y * grad_scale + wd * wv.y; mv.y = mu * mv.y + gg; wv.y -= lr * mv.y;
-    gg = gv.z * grad_scale + wd * wv.z; mv.z = mu * mv.z + gg; wv.z -= lr * mv.z;
-    gg = gv.w * grad_scale + wd * wv.w; mv.w = mu * mv.w + gg; wv.w -= lr * mv.w;
-  };
+  const MomentumUpd upd{lr, mu, wd, grad_scale};
   auto store = [&](int64_t i, const float4& wv, const float4& mv) {
     reinterpret_cast<float4*>(w)[i] = wv;
     reinterpret_cast<float4*>(m)[i] = mv;
@@ -57,8 +73,8 @@ __global__ __launch_bounds__(256) void sgd_momentum_kernel(float* __restrict__ w
     float4 w0 = reinterpret_cast<float4*>(w)[i], w1 = reinterpret_cast<float4*>(w)[i + stride];
     float4 m0 = reinterpret_cast<float4*>(m)[i], m1 = reinterpret_cast<float4*>(m)[i + stride];
     const float4 g0 = grad4(g, i), g1 = grad4(g, i + stride);
-    upd(w0, m0, g0);
-    upd(w1, m1, g1);
+    upd4(upd, w0, m0, g0);
+    upd4(upd, w1, m1, g1);
     store(i, w0, m0);
     store(i + stride, w1, m1);
   }
@@ -66,7 +82,7 @@ __global__ __launch_bounds__(256) void sgd_momentum_kernel(float* __restrict__ w
     float4 w0 = reinterpret_cast<float4*>(w)[i];
     float4 m0 = reinterpret_cast<float4*>(m)[i];
     const float4 g0 = grad4(g, i);
-    upd(w0, m0, g0);
+    upd4(upd, w0, m0, g0);
     store(i, w0, m0);
   }
 }
@@ -191,14 +207,7 @@ __global__ __launch_bounds__(256) void lars_update_kernel(float* __restrict__ w,
     }
     if (c == 0 && threadIdx.x == 0) trust_out[slot] = trust;
     // with trust == 1 bit for bit the update of sgd_momentum_kernel
-    auto upd1 = [&](float& wv, float& mv, float gv) {
-      const float gg = trust * (gv * grad_scale + wd * wv);
-      mv = __builtin_fmaf(mu, mv, gg);
-      wv -= lr * mv;
-    };
-    auto upd = [&](float4& wv, float4& mv, const float4& gv) {
-      upd1(wv.x, mv.x, gv.x); upd1(wv.y, mv.y, gv.y); upd1(wv.z, mv.z, gv.z); upd1(wv.w, mv.w, gv.w);
-    };
+    const LarsUpd upd{lr, mu, wd, grad_scale, trust};
     auto store = [&](int64_t i, const float4& wv, const float4& mv) {
       reinterpret_cast<float4*>(w)[i] = wv;
       reinterpret_cast<float4*>(m)[i] = mv;
@@ -220,8 +229,8 @@ __global__ __launch_bounds__(256) void lars_update_kernel(float* __restrict__ w,
       float4 w0 = reinterpret_cast<float4*>(w)[p], w1 = reinterpret_cast<float4*>(w)[q];
       float4 m0 = reinterpret_cast<float4*>(m)[p], m1 = reinterpret_cast<float4*>(m)[q];
       const float4 g0 = grad4(g, p), g1 = grad4(g, q);
-      upd(w0, m0, g0);
-      upd(w1, m1, g1);
+      upd4(upd, w0, m0, g0);
+      upd4(upd, w1, m1, g1);
       store(p, w0, m0);
       store(q, w1, m1);
     }
@@ -230,14 +239,14 @@ __global__ __launch_bounds__(256) void lars_update_kernel(float* __restrict__ w,
       float4 w0 = reinterpret_cast<float4*>(w)[p];
       float4 m0 = reinterpret_cast<float4*>(m)[p];
       const float4 g0 = grad4(g, p);
-      upd(w0, m0, g0);
+      upd4(upd, w0, m0, g0);
       store(p, w0, m0);
     }
     if (threadIdx.x == 0 && (full4 << 2) < d.numel && i0 + LARS_CHUNK4 > full4 && i0 <= full4) {
       for (int e = full4 << 2; e < d.numel; ++e) {
         const int64_t p = d.offset + e;
         float wv = w[p], mv = m[p];
-        upd1(wv, mv, grad1(g, p));
+        upd(wv, mv, grad1(g, p));
         w[p] = wv;
         m[p] = mv;
         if (wb) wb[p] = f2bf(wv);
@@ -251,10 +260,12 @@ __global__ __launch_bounds__(256) void lars_update_kernel(float* __restrict__ w,
 // the freshly updated fp32 weight while it is still in a register -- one more read-modify-write
 // stream in the optimizer's pass instead of a separate pass re-reading the master buffer. The decay
 // d is read from device memory like the learning rate, so a captured graph / recorded plan replays
-// with the warm-up value the host wrote for that step. These are kernels of their own (the update
-// arithmetic repeats sgd_momentum_kernel / lars_update_kernel statement for statement, so w, m and
-// wb come out bit-identical): with the EMA off a step launches exactly the kernels above, whose
-// code these leave untouched.
+// with the warm-up value the host wrote for that step. These are kernels of their own: the element
+// update is the MomentumUpd / LarsUpd of sgd_momentum_kernel / lars_update_kernel, so w, m and wb
+// come out bit-identical, but the loads, stores and loops are repeated here. Calling one shared
+// body, or shared load / store / range helpers, from thin kernels was tried and changes the machine
+// code of the plain kernels (profiles/optimizer_loss_refactor_codegen.txt); with the EMA off a step
+// launches exactly the kernels above, with the code they had.
 __device__ __forceinline__ void ema1(float& e, float wv, float om) { e -= om * (e - wv); }
 __device__ __forceinline__ void ema4(float4& e, const float4& wv, float om) {
   ema1(e.x, wv.x, om); ema1(e.y, wv.y, om); ema1(e.z, wv.z, om); ema1(e.w, wv.w, om);
@@ -270,13 +281,7 @@ __global__ __launch_bounds__(256) void sgd_momentum_ema_kernel(float* __restrict
   if (skip != nullptr && *skip != 0) return;  // the average is skipped with the update
   const float lr = *lr_ptr;
   const float om = 1.f - *decay_ptr;
-  auto upd = [&](float4& wv, float4& mv, const float4& gv) {
-    float gg;
-    gg = gv.x * grad_scale + wd * wv.x; mv.x = mu * mv.x + gg; wv.x -= lr * mv.x;
-    gg = gv.y * grad_scale + wd * wv.y; mv.y = mu * mv.y + gg; wv.y -= lr * mv.y;
-    gg = gv.z * grad_scale + wd * wv.z; mv.z = mu * mv.z + gg; wv.z -= lr * mv.z;
-    gg = gv.w * grad_scale + wd * wv.w; mv.w = mu * mv.w + gg; wv.w -= lr * mv.w;
-  };
+  const MomentumUpd upd{lr, mu, wd, grad_scale};
   auto store = [&](int64_t i, const float4& wv, const float4& mv, const float4& ev) {
     reinterpret_cast<float4*>(w)[i] = wv;
     reinterpret_cast<float4*>(m)[i] = mv;
@@ -296,8 +301,8 @@ __global__ __launch_bounds__(256) void sgd_momentum_ema_kernel(float* __restrict
     float4 m0 = reinterpret_cast<float4*>(m)[i], m1 = reinterpret_cast<float4*>(m)[i + stride];
     float4 e0 = reinterpret_cast<float4*>(ema)[i], e1 = reinterpret_cast<float4*>(ema)[i + stride];
     const float4 g0 = grad4(g, i), g1 = grad4(g, i + stride);
-    upd(w0, m0, g0);
-    upd(w1, m1, g1);
+    upd4(upd, w0, m0, g0);
+    upd4(upd, w1, m1, g1);
     ema4(e0, w0, om);
     ema4(e1, w1, om);
     store(i, w0, m0, e0);
@@ -308,7 +313,7 @@ __global__ __launch_bounds__(256) void sgd_momentum_ema_kernel(float* __restrict
     float4 m0 = reinterpret_cast<float4*>(m)[i];
     float4 e0 = reinterpret_cast<float4*>(ema)[i];
     const float4 g0 = grad4(g, i);
-    upd(w0, m0, g0);
+    upd4(upd, w0, m0, g0);
     ema4(e0, w0, om);
     store(i, w0, m0, e0);
   }
@@ -349,14 +354,7 @@ __global__ __launch_bounds__(256) void lars_update_ema_kernel(float* __restrict_
       }
     }
     if (c == 0 && threadIdx.x == 0) trust_out[slot] = trust;
-    auto upd1 = [&](float& wv, float& mv, float gv) {
-      const float gg = trust * (gv * grad_scale + wd * wv);
-      mv = __builtin_fmaf(mu, mv, gg);
-      wv -= lr * mv;
-    };
-    auto upd = [&](float4& wv, float4& mv, const float4& gv) {
-      upd1(wv.x, mv.x, gv.x); upd1(wv.y, mv.y, gv.y); upd1(wv.z, mv.z, gv.z); upd1(wv.w, mv.w, gv.w);
-    };
+    const LarsUpd upd{lr, mu, wd, grad_scale, trust};
     auto store = [&](int64_t i, const float4& wv, const float4& mv, const float4& ev) {
       reinterpret_cast<float4*>(w)[i] = wv;
       reinterpret_cast<float4*>(m)[i] = mv;
@@ -379,8 +377,8 @@ __global__ __launch_bounds__(256) void lars_update_ema_kernel(float* __restrict_
       float4 m0 = reinterpret_cast<float4*>(m)[p], m1 = reinterpret_cast<float4*>(m)[q];
       float4 e0 = reinterpret_cast<float4*>(ema)[p], e1 = reinterpret_cast<float4*>(ema)[q];
       const float4 g0 = grad4(g, p), g1 = grad4(g, q);
-      upd(w0, m0, g0);
-      upd(w1, m1, g1);
+      upd4(upd, w0, m0, g0);
+      upd4(upd, w1, m1, g1);
       ema4(e0, w0, om);
       ema4(e1, w1, om);
       store(p, w0, m0, e0);
@@ -392,7 +390,7 @@ __global__ __launch_bounds__(256) void lars_update_ema_kernel(float* __restrict_
       float4 m0 = reinterpret_cast<float4*>(m)[p];
       float4 e0 = reinterpret_cast<float4*>(ema)[p];
       const float4 g0 = grad4(g, p);
-      upd(w0, m0, g0);
+      upd4(upd, w0, m0, g0);
       ema4(e0, w0, om);
       store(p, w0, m0, e0);
     }
@@ -400,7 +398,7 @@ __global__ __launch_bounds__(256) void lars_update_ema_kernel(float* __restrict_
       for (int e = full4 << 2; e < d.numel; ++e) {
         const int64_t p = d.offset + e;
         float wv = w[p], mv = m[p], ev = ema[p];
-        upd1(wv, mv, grad1(g, p));
+        upd(wv, mv, grad1(g, p));
         ema1(ev, wv, om);
         w[p] = wv;
         m[p] = mv;
@@ -502,19 +500,60 @@ static inline int grid_for(int64_t n) {
 
 }  // namespace drn
 
+// f(gradient pointer typed by g_bf16): bf16 (the all-reduced bf16 wire buffer), else fp32
+template <typename F>
+static void with_grad_type(const void* g, int g_bf16, F&& f) {
+  if (g_bf16) f((const bf16_t*)g); else f((const float*)g);
+}
+template <typename P>
+using grad_t = std::remove_const_t<std::remove_pointer_t<P>>;
+
+// ema == nullptr: the plain kernel
+static int sgd_momentum(float* w, float* m, const void* g, int g_bf16, void* w_bf16, int64_t n, const float* lr_ptr,
+                        float momentum, float wd, float grad_scale, const int* skip, float* ema,
+                        const float* decay_ptr, hipStream_t s) {
+  if (n % 4) return (int)hipErrorInvalidValue;
+  const dim3 grid(drn::grid_for(n / 4)), block(256);
+  with_grad_type(g, g_bf16, [&](auto gp) {
+    using G = grad_t<decltype(gp)>;
+    if (ema)
+      drn::launch(drn::sgd_momentum_ema_kernel<G>, grid, block, 0, s, w, m, gp, (bf16_t*)w_bf16, n / 4, lr_ptr,
+                  momentum, wd, grad_scale, skip, ema, decay_ptr);
+    else
+      drn::launch(drn::sgd_momentum_kernel<G>, grid, block, 0, s, w, m, gp, (bf16_t*)w_bf16, n / 4, lr_ptr, momentum,
+                  wd, grad_scale, skip);
+  });
+  return (int)hipGetLastError();
+}
+
+// the norms pass, then the update pass; ema == nullptr: the plain update kernel
+static int lars_momentum(float* w, float* m, const void* g, int g_bf16, void* w_bf16, const void* table,
+                         int first_slot, int nslots, float* partials, float* trust, const float* lr_ptr,
+                         float momentum, float wd, float grad_scale, float eta, float eps, const int* skip,
+                         float* ema, const float* decay_ptr, hipStream_t s) {
+  if (first_slot < 0 || nslots < 1) return (int)hipErrorInvalidValue;
+  const drn::LarsSlot* t = (const drn::LarsSlot*)table;
+  const dim3 grid(drn::LARS_GRID), block(256);
+  with_grad_type(g, g_bf16, [&](auto gp) {
+    using G = grad_t<decltype(gp)>;
+    drn::launch(drn::lars_norms_kernel<G>, grid, block, 0, s, (const float*)w, gp, t, first_slot, nslots, partials,
+                grad_scale, skip);
+    if (ema)
+      drn::launch(drn::lars_update_ema_kernel<G>, grid, block, 0, s, w, m, gp, (bf16_t*)w_bf16, t, first_slot, nslots,
+                  (const float*)partials, trust, lr_ptr, momentum, wd, grad_scale, eta, eps, skip, ema, decay_ptr);
+    else
+      drn::launch(drn::lars_update_kernel<G>, grid, block, 0, s, w, m, gp, (bf16_t*)w_bf16, t, first_slot, nslots,
+                  (const float*)partials, trust, lr_ptr, momentum, wd, grad_scale, eta, eps, skip);
+  });
+  return (int)hipGetLastError();
+}
+
 // skip (nullable device int): when *skip != 0 at run time the launch changes nothing;
 // g_bf16: the gradient is bf16 (the all-reduced bf16 wire buffer), else fp32
 DRN_API int drn_sgd_momentum(float* w, float* m, const void* g, int g_bf16, void* w_bf16, int64_t n,
                              const float* lr_ptr, float momentum, float wd, float grad_scale, const int* skip,
                              hipStream_t s) {
-  if (n % 4) return (int)hipErrorInvalidValue;
-  if (g_bf16)
-    drn::launch(drn::sgd_momentum_kernel<bf16_t>, dim3(drn::grid_for(n / 4)), dim3(256), 0, s, w, m,
-                       (const bf16_t*)g, (bf16_t*)w_bf16, n / 4, lr_ptr, momentum, wd, grad_scale, skip);
-  else
-    drn::launch(drn::sgd_momentum_kernel<float>, dim3(drn::grid_for(n / 4)), dim3(256), 0, s, w, m,
-                       (const float*)g, (bf16_t*)w_bf16, n / 4, lr_ptr, momentum, wd, grad_scale, skip);
-  return (int)hipGetLastError();
+  return sgd_momentum(w, m, g, g_bf16, w_bf16, n, lr_ptr, momentum, wd, grad_scale, skip, nullptr, nullptr, s);
 }
 
 // LARS + momentum over table slots [first_slot, first_slot + nslots) of the flat buffers (w, m, g,
@@ -525,21 +564,8 @@ DRN_API int drn_lars_momentum(float* w, float* m, const void* g, int g_bf16, voi
                               int first_slot, int nslots, float* partials, float* trust, const float* lr_ptr,
                               float momentum, float wd, float grad_scale, float eta, float eps, const int* skip,
                               hipStream_t s) {
-  if (first_slot < 0 || nslots < 1) return (int)hipErrorInvalidValue;
-  const drn::LarsSlot* t = (const drn::LarsSlot*)table;
-  const dim3 grid(drn::LARS_GRID), block(256);
-  if (g_bf16) {
-    drn::launch(drn::lars_norms_kernel<bf16_t>, grid, block, 0, s, (const float*)w, (const bf16_t*)g, t, first_slot,
-                nslots, partials, grad_scale, skip);
-    drn::launch(drn::lars_update_kernel<bf16_t>, grid, block, 0, s, w, m, (const bf16_t*)g, (bf16_t*)w_bf16, t,
-                first_slot, nslots, (const float*)partials, trust, lr_ptr, momentum, wd, grad_scale, eta, eps, skip);
-  } else {
-    drn::launch(drn::lars_norms_kernel<float>, grid, block, 0, s, (const float*)w, (const float*)g, t, first_slot,
-                nslots, partials, grad_scale, skip);
-    drn::launch(drn::lars_update_kernel<float>, grid, block, 0, s, w, m, (const float*)g, (bf16_t*)w_bf16, t,
-                first_slot, nslots, (const float*)partials, trust, lr_ptr, momentum, wd, grad_scale, eta, eps, skip);
-  }
-  return (int)hipGetLastError();
+  return lars_momentum(w, m, g, g_bf16, w_bf16, table, first_slot, nslots, partials, trust, lr_ptr, momentum, wd,
+                       grad_scale, eta, eps, skip, nullptr, nullptr, s);
 }
 
 // drn_sgd_momentum + the weight EMA in the same launch: ema (n floats, 16-byte aligned like w) <-
@@ -547,14 +573,8 @@ DRN_API int drn_lars_momentum(float* w, float* m, const void* g, int g_bf16, voi
 DRN_API int drn_sgd_momentum_ema(float* w, float* m, const void* g, int g_bf16, void* w_bf16, int64_t n,
                                  const float* lr_ptr, float momentum, float wd, float grad_scale, const int* skip,
                                  float* ema, const float* decay_ptr, hipStream_t s) {
-  if (n % 4 || ema == nullptr || decay_ptr == nullptr) return (int)hipErrorInvalidValue;
-  if (g_bf16)
-    drn::launch(drn::sgd_momentum_ema_kernel<bf16_t>, dim3(drn::grid_for(n / 4)), dim3(256), 0, s, w, m,
-                (const bf16_t*)g, (bf16_t*)w_bf16, n / 4, lr_ptr, momentum, wd, grad_scale, skip, ema, decay_ptr);
-  else
-    drn::launch(drn::sgd_momentum_ema_kernel<float>, dim3(drn::grid_for(n / 4)), dim3(256), 0, s, w, m,
-                (const float*)g, (bf16_t*)w_bf16, n / 4, lr_ptr, momentum, wd, grad_scale, skip, ema, decay_ptr);
-  return (int)hipGetLastError();
+  if (ema == nullptr || decay_ptr == nullptr) return (int)hipErrorInvalidValue;
+  return sgd_momentum(w, m, g, g_bf16, w_bf16, n, lr_ptr, momentum, wd, grad_scale, skip, ema, decay_ptr, s);
 }
 
 // drn_lars_momentum + the weight EMA in its update pass (the norms pass is the same kernel): ema is
@@ -563,23 +583,9 @@ DRN_API int drn_lars_momentum_ema(float* w, float* m, const void* g, int g_bf16,
                                   int first_slot, int nslots, float* partials, float* trust, const float* lr_ptr,
                                   float momentum, float wd, float grad_scale, float eta, float eps, const int* skip,
                                   float* ema, const float* decay_ptr, hipStream_t s) {
-  if (first_slot < 0 || nslots < 1 || ema == nullptr || decay_ptr == nullptr) return (int)hipErrorInvalidValue;
-  const drn::LarsSlot* t = (const drn::LarsSlot*)table;
-  const dim3 grid(drn::LARS_GRID), block(256);
-  if (g_bf16) {
-    drn::launch(drn::lars_norms_kernel<bf16_t>, grid, block, 0, s, (const float*)w, (const bf16_t*)g, t, first_slot,
-                nslots, partials, grad_scale, skip);
-    drn::launch(drn::lars_update_ema_kernel<bf16_t>, grid, block, 0, s, w, m, (const bf16_t*)g, (bf16_t*)w_bf16, t,
-                first_slot, nslots, (const float*)partials, trust, lr_ptr, momentum, wd, grad_scale, eta, eps, skip,
-                ema, decay_ptr);
-  } else {
-    drn::launch(drn::lars_norms_kernel<float>, grid, block, 0, s, (const float*)w, (const float*)g, t, first_slot,
-                nslots, partials, grad_scale, skip);
-    drn::launch(drn::lars_update_ema_kernel<float>, grid, block, 0, s, w, m, (const float*)g, (bf16_t*)w_bf16, t,
-                first_slot, nslots, (const float*)partials, trust, lr_ptr, momentum, wd, grad_scale, eta, eps, skip,
-                ema, decay_ptr);
-  }
-  return (int)hipGetLastError();
+  if (ema == nullptr || decay_ptr == nullptr) return (int)hipErrorInvalidValue;
+  return lars_momentum(w, m, g, g_bf16, w_bf16, table, first_slot, nslots, partials, trust, lr_ptr, momentum, wd,
+                       grad_scale, eta, eps, skip, ema, decay_ptr, s);
 }
 
 DRN_API int drn_lars_slot_size() { return (int)sizeof(drn::LarsSlot); }
