@@ -186,4 +186,9 @@ class Saver:
         meta["imagenet_preprocessing"] = str(meta.get("imagenet_preprocessing", "vgg"))
         meta["rrc_scale_min"] = float(meta.get("rrc_scale_min", 0.08))
         meta["color_jitter"] = float(meta.get("color_jitter", 0.0))
+        # the optimizer: absent = the reference's momentum; Adam's constants at the flag defaults
+        meta["optimizer"] = str(meta.get("optimizer", "momentum"))
+        meta["adam_beta1"] = float(meta.get("adam_beta1", 0.9))
+        meta["adam_beta2"] = float(meta.get("adam_beta2", 0.999))
+        meta["adam_eps"] = float(meta.get("adam_eps", 1e-6))
         return meta

@@ -152,13 +152,23 @@ def validate(fv: "FlagValues") -> None:
     """Cross-flag checks at parse time (flag sets that do not define a flag skip its checks)."""
     if "optimizer" not in fv:
         return
-    if fv.optimizer not in ("momentum", "lars"):
-        raise FlagsError(f"--optimizer must be momentum or lars, got {fv.optimizer!r}")
-    if fv.lr_policy not in ("reference", "poly"):
-        raise FlagsError(f"--lr_policy must be reference or poly, got {fv.lr_policy!r}")
+    if fv.optimizer not in ("momentum", "lars", "adamw", "lamb"):
+        raise FlagsError(f"--optimizer must be momentum, lars, adamw or lamb, got {fv.optimizer!r}")
+    if fv.lr_policy not in ("reference", "poly", "warmup_cosine"):
+        raise FlagsError(f"--lr_policy must be reference, poly or warmup_cosine, got {fv.lr_policy!r}")
     if fv.optimizer == "lars" and fv.optimizer_sharding:
         raise FlagsError("--optimizer=lars cannot be combined with --optimizer_sharding: a sharded update cuts "
                          "tensors across ranks and LARS needs each tensor's whole norm")
+    if fv.optimizer == "lamb" and fv.optimizer_sharding:
+        raise FlagsError("--optimizer=lamb cannot be combined with --optimizer_sharding: a sharded update cuts "
+                         "tensors across ranks and LAMB needs each tensor's whole norms")
+    if fv.optimizer in ("adamw", "lamb") and fv.model == "lrnet":
+        raise FlagsError(f"--optimizer={fv.optimizer} is not supported by --model=lrnet (it trains with its own "
+                         "Adam path)")
+    if not (0.0 <= fv.adam_beta1 < 1.0 and 0.0 <= fv.adam_beta2 < 1.0):
+        raise FlagsError(f"--adam_beta1 and --adam_beta2 must be in [0, 1), got {fv.adam_beta1!r}, {fv.adam_beta2!r}")
+    if not fv.adam_epsilon > 0.0:
+        raise FlagsError(f"--adam_epsilon must be > 0, got {fv.adam_epsilon!r}")
     if not 0.0 <= fv.label_smoothing < 1.0:
         raise FlagsError(f"--label_smoothing must be in [0, 1), got {fv.label_smoothing!r}")
     if fv.top_k < 0:
@@ -283,12 +293,17 @@ def define_reference_flags(flag_values: FlagValues = FLAGS, **defaults) -> FlagV
     B("optimizer_sharding", False, "ZeRO-1-style sharded optimizer (the parameter-server sharding analog, "
       "SURVEY P3): reduce-scatter the gradient buckets, update 1/N of the weights and momentum per rank, "
       "all-gather the bf16 compute weights.", fv)
-    S("optimizer", "momentum", "momentum (the reference's MomentumOptimizer) or lars (layer-wise adaptive rate "
-      "scaling on conv / dense kernels, for large global batches; fused HIP kernels).", fv)
+    S("optimizer", "momentum", "momentum (the reference's MomentumOptimizer), lars (layer-wise adaptive rate "
+      "scaling on conv / dense kernels, for large global batches), adamw (Adam with decoupled weight decay) or "
+      "lamb (Adam's direction scaled per tensor by |w| / |u|); fused HIP kernels.", fv)
+    Fl("adam_beta1", 0.9, "--optimizer=adamw|lamb: decay of the first moment (0 <= b < 1).", fv)
+    Fl("adam_beta2", 0.999, "--optimizer=adamw|lamb: decay of the second moment (0 <= b < 1).", fv)
+    Fl("adam_epsilon", 1e-6, "--optimizer=adamw|lamb: epsilon added to sqrt(v_hat) (> 0).", fv)
     Fl("lars_eta", 0.001, "LARS trust coefficient: trust = eta * |w| / (|g| + wd * |w| + eps).", fv)
     Fl("lars_eps", 1e-9, "LARS epsilon in the trust ratio's denominator.", fv)
-    S("lr_policy", "reference", "reference (the reference scripts' step tables) or poly (linear warm-up from 0 "
-      "to --peak_lr over --warmup_steps, then polynomial decay to --end_lr at --train_steps).", fv)
+    S("lr_policy", "reference", "reference (the reference scripts' step tables), poly (linear warm-up from 0 "
+      "to --peak_lr over --warmup_steps, then polynomial decay to --end_lr at --train_steps) or warmup_cosine "
+      "(the same warm-up, then half a cosine period down to --end_lr at --train_steps).", fv)
     Fl("peak_lr", 0.1, "--lr_policy=poly: learning rate at the end of the warm-up.", fv)
     I("warmup_steps", 0, "--lr_policy=poly: linear warm-up steps.", fv)
     Fl("poly_power", 2.0, "--lr_policy=poly: power of the polynomial decay.", fv)

@@ -134,6 +134,15 @@ _SIGS = {
     "drn_sgd_momentum_ema": ([c_p, c_p, c_p, c_int, c_p, c_i64, c_p, c_f, c_f, c_f, c_p, c_p, c_p, c_p], c_int),
     "drn_lars_momentum_ema": ([c_p, c_p, c_p, c_int, c_p, c_p, c_int, c_int, c_p, c_p, c_p, c_f, c_f, c_f, c_f, c_f,
                                c_p, c_p, c_p, c_p], c_int),
+    # AdamW / LAMB (adam.hip): w, m, v, g, g_bf16, w_bf16, then n | table, first_slot, nslots, partials, trust;
+    # lr_ptr, bc_ptr (c1, c2), b1, b2, eps, wd, grad_scale, skip[, ema, decay_ptr], stream
+    "drn_adamw": ([c_p, c_p, c_p, c_p, c_int, c_p, c_i64, c_p, c_p, c_f, c_f, c_f, c_f, c_f, c_p, c_p], c_int),
+    "drn_adamw_ema": ([c_p, c_p, c_p, c_p, c_int, c_p, c_i64, c_p, c_p, c_f, c_f, c_f, c_f, c_f, c_p, c_p, c_p, c_p],
+                      c_int),
+    "drn_lamb": ([c_p, c_p, c_p, c_p, c_int, c_p, c_p, c_int, c_int, c_p, c_p, c_p, c_p, c_f, c_f, c_f, c_f, c_f,
+                  c_p, c_p], c_int),
+    "drn_lamb_ema": ([c_p, c_p, c_p, c_p, c_int, c_p, c_p, c_int, c_int, c_p, c_p, c_p, c_p, c_f, c_f, c_f, c_f, c_f,
+                      c_p, c_p, c_p, c_p], c_int),
     # global-norm clip + non-finite guard (gradguard.hip): g, g_bf16, n, grad_scale, clip, guard_nonfinite,
     # skip_in, partials, record, stream
     "drn_grad_guard": ([c_p, c_int, c_i64, c_f, c_f, c_int, c_p, c_p, c_p, c_p], c_int),

@@ -1087,6 +1087,52 @@ class HipBackend(_Common):
                                             float(wd), float(grad_scale), float(eta), float(eps), _ptr(skip),
                                             self.stream()), "drn_lars_momentum")
 
+    def adamw(self, w, m, v, g, wb, lr_t, bc_t, b1, b2, eps, wd, grad_scale, skip=None, ema=None, ema_decay_t=None):
+        """Fused AdamW (adam.hip), one launch over the flat range: m, v the fp32 moments, bc_t two
+        device fp32 values (c1, c2) = (1 - b1^t, 1 - b2^t) of this update, lr_t the device LR.
+        u = (m / c1) / (sqrt(v / c2) + eps) + wd * w; w -= lr * u; wb = bf16(w). skip, ema and
+        ema_decay_t as in sgd_momentum."""
+        assert g.dtype in (torch.float32, torch.bfloat16) and g.numel() == w.numel() == m.numel() == v.numel()
+        assert bc_t.dtype == lr_t.dtype == torch.float32 and bc_t.numel() >= 2
+        args = (w.data_ptr(), m.data_ptr(), v.data_ptr(), g.data_ptr(), int(g.dtype == torch.bfloat16), _ptr(wb),
+                w.numel(), lr_t.data_ptr(), bc_t.data_ptr(), float(b1), float(b2), float(eps), float(wd),
+                float(grad_scale), _ptr(skip))
+        if ema is not None:
+            assert ema_decay_t is not None and ema.dtype == ema_decay_t.dtype == torch.float32
+            assert ema.numel() == w.numel() and ema.data_ptr() % 16 == 0
+            _lib.check(self.L.drn_adamw_ema(*args, ema.data_ptr(), ema_decay_t.data_ptr(), self.stream()),
+                       "drn_adamw_ema")
+            return
+        _lib.check(self.L.drn_adamw(*args, self.stream()), "drn_adamw")
+
+    def lamb(self, w, m, v, g, wb, table: LarsTable, first_slot, nslots, partials, trust, lr_t, bc_t, b1, b2, eps, wd,
+             grad_scale, skip=None, ema=None, ema_decay_t=None):
+        """Fused LAMB (adam.hip; two launches) on slots [first_slot, first_slot + nslots) of `table`:
+        Adam's moments and direction u as in adamw, w -= lr * trust * u with the per-slot
+        trust = ||w|| / ||u|| (1 if a norm is 0 or the slot does not adapt). Buffers, table, partials
+        and trust as in lars_momentum; skip leaves everything alone, trust included."""
+        assert g.dtype in (torch.float32, torch.bfloat16) and g.numel() == w.numel() == m.numel() == v.numel()
+        assert 0 <= first_slot and nslots >= 1 and first_slot + nslots <= table.n
+        assert int(table.arr["offset"][table.n]) <= w.numel() and table.dev.device == w.device
+        assert partials.numel() >= 2 * table.chunks and trust.numel() >= table.n
+        assert partials.dtype == trust.dtype == torch.float32 and (wb is None or wb.numel() == w.numel())
+        assert bc_t.dtype == lr_t.dtype == torch.float32 and bc_t.numel() >= 2
+        if not getattr(self, "_lars_checked", False):
+            if self.L.drn_lars_slot_size() != LARS_SLOT.itemsize or self.L.drn_lars_chunk() != LARS_CHUNK:
+                raise _lib.KernelLibraryError("LarsSlot layout mismatch between Python and the kernel library")
+            self._lars_checked = True
+        args = (w.data_ptr(), m.data_ptr(), v.data_ptr(), g.data_ptr(), int(g.dtype == torch.bfloat16), _ptr(wb),
+                table.dev.data_ptr(), int(first_slot), int(nslots), partials.data_ptr(), trust.data_ptr(),
+                lr_t.data_ptr(), bc_t.data_ptr(), float(b1), float(b2), float(eps), float(wd), float(grad_scale),
+                _ptr(skip))
+        if ema is not None:
+            assert ema_decay_t is not None and ema.dtype == ema_decay_t.dtype == torch.float32
+            assert ema.numel() == w.numel() and ema.data_ptr() % 16 == 0
+            _lib.check(self.L.drn_lamb_ema(*args, ema.data_ptr(), ema_decay_t.data_ptr(), self.stream()),
+                       "drn_lamb_ema")
+            return
+        _lib.check(self.L.drn_lamb(*args, self.stream()), "drn_lamb")
+
     def grad_guard(self, g, grad_scale, clip, guard_nonfinite, skip_in, partials, record):
         """Global-norm clipping + the non-finite step guard of the flat gradient g (fp32 or bf16,
         16-byte aligned) that the optimizer will scale by grad_scale (gradguard.hip; two launches):
@@ -1593,6 +1639,52 @@ class RefBackend(_Common):
                 gg = gg * t
             ms.mul_(momentum).add_(gg)
             ws.sub_(lr * ms)
+            if wb is not None and wb.data_ptr() != w.data_ptr():
+                wb[sl].copy_(ws)
+            if ema is not None:
+                self._ema(ema[sl], ws, ema_decay_t)
+            trust[i] = t
+
+    @staticmethod
+    def _adam_dir(w, m, v, g, bc_t, b1, b2, eps, wd, grad_scale):
+        """m, v <- Adam's moments of g' = grad_scale * g (in place); returns the update direction
+        u = (m / c1) / (sqrt(v / c2) + eps) + wd * w, everything in the dtype of w."""
+        c1, c2 = float(bc_t.reshape(-1)[0]), float(bc_t.reshape(-1)[1])
+        gg = g.to(w.dtype) * grad_scale
+        m.mul_(b1).add_(gg * (1.0 - b1))
+        v.mul_(b2).add_(gg * gg * (1.0 - b2))
+        return (m / c1) / (torch.sqrt(v / c2) + eps) + wd * w
+
+    def adamw(self, w, m, v, g, wb, lr_t, bc_t, b1, b2, eps, wd, grad_scale, skip=None, ema=None, ema_decay_t=None):
+        """HipBackend.adamw's contract in torch, in the dtype of w (the oracle: fp64 under
+        RefBackend(dtype=torch.float64), with an fp64 bc_t)."""
+        if skip is not None and int(skip.reshape(-1)[0]) != 0:
+            return
+        lr = float(lr_t.reshape(-1)[0])
+        u = self._adam_dir(w, m, v, g, bc_t, b1, b2, eps, wd, grad_scale)
+        w.sub_(lr * u)
+        if wb is not None and wb.data_ptr() != w.data_ptr():
+            wb.copy_(w)
+        if ema is not None:
+            self._ema(ema, w, ema_decay_t)
+
+    def lamb(self, w, m, v, g, wb, table: LarsTable, first_slot, nslots, partials, trust, lr_t, bc_t, b1, b2, eps, wd,
+             grad_scale, skip=None, ema=None, ema_decay_t=None):
+        """HipBackend.lamb's contract in torch, in the dtype of w. partials is not used."""
+        if skip is not None and int(skip.reshape(-1)[0]) != 0:
+            return
+        lr = float(lr_t.reshape(-1)[0])
+        for i in range(first_slot, first_slot + nslots):
+            d = table.arr[i]
+            sl = slice(int(d["offset"]), int(d["offset"]) + int(d["numel"]))
+            ws = w[sl]
+            u = self._adam_dir(ws, m[sl], v[sl], g[sl], bc_t, b1, b2, eps, wd, grad_scale)
+            t = 1.0
+            if d["adapt"]:
+                wn, un = float(torch.linalg.vector_norm(ws)), float(torch.linalg.vector_norm(u))
+                if wn > 0 and un > 0:
+                    t = wn / un
+            ws.sub_((lr * t) * u)
             if wb is not None and wb.data_ptr() != w.data_ptr():
                 wb[sl].copy_(ws)
             if ema is not None:

@@ -134,8 +134,9 @@ class DataParallelEngine:
                 self.buckets = self._make_buckets(int(self.P.total // 60) + 1)
             self.p2p = P2PAllReduce(self.P.grad, group, wire=self.wire)
         self.zero1 = bool(shard_optimizer) and self.world > 1 and mode == "sync"
-        if self.zero1 and getattr(executor, "optimizer", "momentum") == "lars":
-            raise ValueError("optimizer sharding cuts tensors across ranks; LARS needs each tensor's whole norm")
+        if self.zero1 and getattr(executor, "optimizer", "momentum") in ("lars", "lamb"):
+            raise ValueError("optimizer sharding cuts tensors across ranks; LARS needs each tensor's whole norm "
+                             "(and so does LAMB)")
         if self.zero1 and self.wire != "fp32":
             raise ValueError("optimizer sharding reduce-scatters fp32 gradients (--allreduce_wire=fp32)")
         # RCCL bf16 wire: a bf16 shadow of the flat gradient; each bucket is cast into it by an
@@ -338,13 +339,19 @@ class DataParallelEngine:
             w.wait()
         self.ex.refresh_dgrad_weights()
 
+    def _adam_state(self) -> tuple:
+        """Adam's second moment, when an Adam-family optimizer keeps one."""
+        v = getattr(self.P, "adam_v", None)
+        return () if v is None else (v,)
+
     def gather_state(self):
         """ZeRO-1: make the fp32 masters, momentum and weight EMA (each rank averages its shards
         only) complete on every rank (collective; before a checkpoint or anything else that reads
         them). No-op otherwise."""
         if not self.zero1:
             return
-        for t in (self.P.master, self.P.momentum) + ((self.P.ema,) if self.P.ema is not None else ()):
+        for t in (self.P.master, self.P.momentum) + ((self.P.ema,) if self.P.ema is not None else ()) \
+                + self._adam_state():
             for lo, hi in self.buckets:
                 if self._sharded(lo, hi):
                     s0, s1 = self._shard(lo, hi)
@@ -414,12 +421,16 @@ class DataParallelEngine:
     # -- state sync -----------------------------------------------------------------------------------
     def broadcast_parameters(self, src: int = 0):
         """Rank-0 broadcast of every variable (Horovod BroadcastGlobalVariablesHook(0) analog)."""
-        for t in (self.P.master, self.P.momentum, self.P.bn_state) + ((self.P.ema,) if self.P.ema is not None else ()):
+        for t in (self.P.master, self.P.momentum, self.P.bn_state) + ((self.P.ema,) if self.P.ema is not None else ()) \
+                + self._adam_state():
             dist.broadcast(t, src=src, group=self.group)
-        step = torch.tensor([self.P.global_step], dtype=torch.int64,
+        step = torch.tensor([self.P.global_step, getattr(self.P, "adam_t0", 0)], dtype=torch.int64,
                             device=self.P.master.device)
         dist.broadcast(step, src=src, group=self.group)
-        self.P.global_step = int(step.item())
+        self.P.global_step = int(step[0].item())
+        if self._adam_state():
+            self.P.adam_t0 = int(step[1].item())
+            self.ex.set_adam_step(self.P.global_step)
         self.ex.sync_weights()
 
     def average_bn_state(self):

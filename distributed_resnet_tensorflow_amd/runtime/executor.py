@@ -107,7 +107,8 @@ class Executor:
                  materialize_bn: Optional[bool] = None, optimizer: str = "momentum", lars_eta: float = 0.001,
                  lars_eps: float = 1e-9, label_smoothing: float = 0.0, top_k: int = 0, ema_decay: float = 0.0,
                  ema_warmup: bool = True, mix: bool = False, clip_grad_norm: float = 0.0,
-                 skip_nonfinite_grads: bool = False):
+                 skip_nonfinite_grads: bool = False, adam_beta1: float = 0.9, adam_beta2: float = 0.999,
+                 adam_eps: float = 1e-6):
         self.spec, self.N, self.be = spec, batch, backend
         # clip_grad_norm = c > 0: the gradient the optimizer reads is scaled by c / max(norm, c), norm
         # its global L2 norm (grad_scale included; TF's clip_by_global_norm). skip_nonfinite_grads: a
@@ -129,9 +130,19 @@ class Executor:
         # "momentum": the reference's MomentumOptimizer; "lars": the same update with each conv /
         # dense kernel's gradient (weight decay included) scaled by its layer-wise trust ratio
         # eta * ||w|| / (||g|| + wd * ||w|| + eps) (csrc/kernels/sgd.hip), for large global batches
-        if optimizer not in ("momentum", "lars"):
-            raise ValueError(f"optimizer must be 'momentum' or 'lars', got {optimizer!r}")
+        # "adamw": Adam with decoupled weight decay; "lamb": the same direction u scaled per tensor by
+        # ||w|| / ||u|| (csrc/kernels/adam.hip). Both keep fp32 moments: P.momentum is the first,
+        # P.adam_v the second (allocated only for them), and the bias corrections of the coming
+        # update are device values like the LR (set_adam_step)
+        if optimizer not in ("momentum", "lars", "adamw", "lamb"):
+            raise ValueError(f"optimizer must be 'momentum', 'lars', 'adamw' or 'lamb', got {optimizer!r}")
         self.optimizer, self.lars_eta, self.lars_eps = optimizer, float(lars_eta), float(lars_eps)
+        self.adam = optimizer in ("adamw", "lamb")
+        if not (0.0 <= adam_beta1 < 1.0 and 0.0 <= adam_beta2 < 1.0):
+            raise ValueError(f"adam_beta1 / adam_beta2 must be in [0, 1), got {adam_beta1!r}, {adam_beta2!r}")
+        if not adam_eps > 0.0:
+            raise ValueError(f"adam_eps must be > 0, got {adam_eps!r}")
+        self.adam_beta1, self.adam_beta2, self.adam_eps = float(adam_beta1), float(adam_beta2), float(adam_eps)
         # label_smoothing: the training target is (1 - eps) one-hot + eps / num_classes; top_k >= 2:
         # correct_k[n] = the label is among the k largest logits (0 / 1: top-1 only). Both come out
         # of the head's one loss kernel (csrc/kernels/head.hip softmax_xent_ex_kernel); with the
@@ -255,9 +266,11 @@ class Executor:
         self._pre_ev, self._pre_lo = None, 0
         self.fdt = backend.acc_dtype
         self.P = params or ParamStore(spec, self.device, keep_bf16=self.is_hip, seed=seed, dtype=self.fdt,
-                                      ema=self.ema_decay > 0)
+                                      ema=self.ema_decay > 0, adam=self.adam)
         if self.ema_decay > 0:
             self.P.enable_ema()   # (a store handed in without the buffer)
+        if self.adam:
+            self.P.enable_adam()
         self.grad_ready: Optional[Callable[[int], None]] = None
         self._alloc()
         self.sync_weights()
@@ -567,11 +580,16 @@ class Executor:
         # LARS: the slot table, the norms workspace and the per-slot trust ratios, allocated once
         # (a captured graph / recorded plan replays with these pointers)
         self.lars_table = self.lars_partials = self.lars_trust = None
-        if self.optimizer == "lars":
+        if self.optimizer in ("lars", "lamb"):   # (LAMB runs over the same table and workspaces)
             from ..ops.backend import lars_table
             self.lars_table = lars_table(self.P, self.device)
             self.lars_partials = self._f32(2 * self.lars_table.chunks)
             self.lars_trust = torch.ones(self.lars_table.n, dtype=torch.float32, device=self.device)
+        # Adam's bias corrections (c1, c2) of the coming update: device memory like the LR
+        self.adam_bc_t = None
+        if self.adam:
+            self.adam_bc_t = self._f32(2)
+            self.set_adam_step(self.P.global_step)
         # gradient guard: the device record (norm, scale, skip word, counters) and the per-workgroup
         # partial sums, allocated once like the LARS workspaces
         self.guard_record = self.guard_partials = None
@@ -1053,6 +1071,21 @@ class Executor:
         if self.ema_decay_t is not None:
             self.be.fill_(self.ema_decay_t, self.ema_decay_at(int(step)))
 
+    def adam_bias_corrections(self, step: int) -> tuple:
+        """(c1, c2) = (1 - b1^t, 1 - b2^t), in fp64, of the update that follows `step` completed
+        updates: t = step - P.adam_t0 + 1 counts the updates since the moments were zero."""
+        t = max(int(step) - int(self.P.adam_t0), 0) + 1
+        return 1.0 - self.adam_beta1 ** t, 1.0 - self.adam_beta2 ** t
+
+    def set_adam_step(self, step: int):
+        """Write the coming update's Adam bias corrections (wherever the LR is written per step), so
+        graph and plan replays use the corrections of their step. A skipped step (guard or P2P error
+        word) still advances t, like global_step and the LR schedule. No-op for momentum / LARS."""
+        if self.adam_bc_t is not None:
+            c1, c2 = self.adam_bias_corrections(step)
+            self.be.fill_(self.adam_bc_t[0:1], c1)
+            self.be.fill_(self.adam_bc_t[1:2], c2)
+
     def join_grads(self):
         """Make the current stream wait for a stem weight gradient deferred by backward() (its
         event only: work queued on the side stream after it -- the data-gradient weight refresh
@@ -1077,12 +1110,25 @@ class Executor:
                                       self.lars_partials, self.lars_trust, self.lr_t, self.mom, self.wd, grad_scale,
                                       self.lars_eta, self.lars_eps, skip, ema=P.ema, ema_decay_t=self.ema_decay_t)
             return
+        if self.optimizer == "lamb":
+            first, n = self.lars_table.slot_range(lo, hi)
+            ema = {} if P.ema is None else dict(ema=P.ema, ema_decay_t=self.ema_decay_t)
+            self.be.lamb(P.master, P.momentum, P.adam_v, g, P.wbf16, self.lars_table, first, n, self.lars_partials,
+                         self.lars_trust, self.lr_t, self.adam_bc_t, self.adam_beta1, self.adam_beta2, self.adam_eps,
+                         self.wd, grad_scale, skip, **ema)
+            return
         self._sgd(lo, hi, g, grad_scale, skip)
 
     def _sgd(self, lo: int, hi: int, g: torch.Tensor, grad_scale: float, skip=None):
         """SGD-momentum on the flat range [lo, hi) (+ its slice of the EMA when that is kept)."""
         P = self.P
         wb = P.wbf16[lo:hi] if P.wbf16 is not None else None
+        if self.optimizer == "adamw":   # element-wise like the momentum update: any flat slice
+            ema = {} if P.ema is None else dict(ema=P.ema[lo:hi], ema_decay_t=self.ema_decay_t)
+            self.be.adamw(P.master[lo:hi], P.momentum[lo:hi], P.adam_v[lo:hi], g[lo:hi], wb, self.lr_t,
+                          self.adam_bc_t, self.adam_beta1, self.adam_beta2, self.adam_eps, self.wd, grad_scale, skip,
+                          **ema)
+            return
         if P.ema is None:
             self.be.sgd_momentum(P.master[lo:hi], P.momentum[lo:hi], g[lo:hi], wb, self.lr_t, self.mom, self.wd,
                                  grad_scale, skip)
@@ -1133,9 +1179,9 @@ class Executor:
 
     def sgd_range(self, lo: int, hi: int, grad_scale: float, grad: Optional[torch.Tensor] = None):
         """Fused SGD-momentum on the flat slice [lo, hi) only (sharded optimizer)."""
-        if self.optimizer == "lars":
+        if self.optimizer in ("lars", "lamb"):
             raise RuntimeError("the sharded optimizer cuts tensors across ranks; LARS needs every tensor's whole "
-                               "norm (optimizer='lars' does not support optimizer sharding)")
+                               f"norm (optimizer={self.optimizer!r} does not support optimizer sharding)")
         if self.guarding:
             raise RuntimeError("a shard sees only part of the gradient; clip_grad_norm / skip_nonfinite_grads need "
                                "its global norm (they do not support optimizer sharding)")
@@ -1241,6 +1287,7 @@ class Executor:
         if lr is not None:
             self.set_lr(lr)
         self.set_ema_decay(self.P.global_step)
+        self.set_adam_step(self.P.global_step)
         self.forward(train=True)
         self.backward(defer_tail=allreduce is None and not self.check_nan)
         if self.check_nan:

@@ -56,7 +56,7 @@ def _trunc_normal(shape, std, gen):
 
 class ParamStore:
     def __init__(self, spec: NetSpec, device, keep_bf16: bool, seed: int = 0, dtype=torch.float32,
-                 ema: bool = False):
+                 ema: bool = False, adam: bool = False):
         self.spec = spec
         self.device = torch.device(device)
         self.slots: list[Slot] = []
@@ -84,6 +84,12 @@ class ParamStore:
         # exponential moving average of the trainable variables (tf.train.ExponentialMovingAverage's
         # shadow variables) in the master's layout; allocated only when the average is kept
         self.ema = torch.zeros(self.total, **f32) if ema else None
+        # Adam-family optimizers (adamw, lamb): the second moment in the master's layout (the first
+        # moment lives in `momentum`), allocated only when one is selected; adam_t0 is the
+        # global_step at which both moments were last zero-initialised (the bias corrections of
+        # update number s use t = s - adam_t0 + 1)
+        self.adam_v = torch.zeros(self.total, **f32) if adam else None
+        self.adam_t0 = 0
         # BN moving statistics (non-trainable), one flat buffer: [mean | var] per BN
         self.bn_slots = {}
         boff = 0
@@ -134,6 +140,9 @@ class ParamStore:
         self.master.copy_(host)
         self.seed_ema()
         self.momentum.zero_()
+        if self.adam_v is not None:
+            self.adam_v.zero_()
+        self.adam_t0 = 0
         self.grad.zero_()
         bs = torch.zeros_like(self.bn_state, device="cpu")
         for name, (off, c) in self.bn_slots.items():
@@ -145,6 +154,13 @@ class ParamStore:
         """Allocate the EMA buffer (once), starting equal to the variables."""
         if self.ema is None:
             self.ema = self.master.clone()
+
+    def enable_adam(self):
+        """Allocate the second-moment buffer (once), zeroed: the moments start at this step."""
+        if self.adam_v is None:
+            self.adam_v = torch.zeros_like(self.master)
+            self.momentum.zero_()
+            self.adam_t0 = self.global_step
 
     def seed_ema(self, name: str | None = None):
         """Shadow values start equal to the variables: all of them, or variable `name` only."""

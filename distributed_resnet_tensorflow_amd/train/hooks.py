@@ -115,12 +115,13 @@ class SummaryHook(Hook):
                             "grad/clipped_steps": m["grad_clipped_steps"],
                             "grad/skipped_steps": m["grad_skipped_steps"]})
         ex = getattr(sess, "ex", None)
-        if getattr(ex, "optimizer", "momentum") == "lars":
+        opt = getattr(ex, "optimizer", "momentum")
+        if opt in ("lars", "lamb"):
             # the last update's trust ratios of the adapting (conv / dense kernel) slots
             adapt = ex.lars_table.arr["adapt"][:ex.lars_table.n] != 0
             t = ex.lars_trust.detach().cpu().numpy()[adapt].astype("float64")
-            scalars.update({"lars/trust_min": float(t.min()), "lars/trust_max": float(t.max()),
-                            "lars/trust_mean": float(t.mean())})
+            scalars.update({f"{opt}/trust_min": float(t.min()), f"{opt}/trust_max": float(t.max()),
+                            f"{opt}/trust_mean": float(t.mean())})
         self.w.add_scalars(step, scalars)
 
     def end(self, sess):

@@ -5,6 +5,8 @@ The reference feeds `lrn_rate` each step from the global step of the PREVIOUS ru
 """
 from __future__ import annotations
 
+import math
+
 
 def cifar_lr(step: int) -> float:
     """resnet_cifar_main.py:287-307: 0.1 -> 0.01 @40k -> 0.001 @60k -> 1e-4 @80k."""
@@ -80,8 +82,30 @@ def poly(peak_lr: float, warmup_steps: int, train_steps: int, power: float = 2.0
     return LRSchedule(fn, fn(0))
 
 
+def cosine_lr(step: int, peak_lr: float, warmup_steps: int, train_steps: int, end_lr: float = 0.0) -> float:
+    """Linear warm-up 0 -> peak_lr over warmup_steps, then half a cosine period
+    end_lr + (peak_lr - end_lr) * 0.5 * (1 + cos(pi * frac)), frac as in poly_lr (the schedule of
+    the AdamW / LAMB recipes; end_lr from train_steps on)."""
+    if step < warmup_steps:
+        return peak_lr * step / warmup_steps
+    span = max(1, train_steps - warmup_steps)
+    frac = min(1.0, (step - warmup_steps) / span)
+    return end_lr + (peak_lr - end_lr) * 0.5 * (1.0 + math.cos(math.pi * frac))
+
+
+def cosine(peak_lr: float, warmup_steps: int, train_steps: int, end_lr: float = 0.0) -> LRSchedule:
+    """The cosine policy under the LRSchedule protocol, as poly()."""
+    if warmup_steps < 0 or train_steps <= warmup_steps:
+        raise ValueError(f"--lr_policy=warmup_cosine needs 0 <= warmup_steps < train_steps, got {warmup_steps}, "
+                         f"{train_steps}")
+    fn = lambda step: cosine_lr(step, peak_lr, warmup_steps, train_steps, end_lr)  # noqa: E731
+    return LRSchedule(fn, fn(0))
+
+
 def from_flags(FLAGS) -> LRSchedule:
-    """--lr_policy=reference: for_dataset; poly: the warm-up / polynomial-decay schedule."""
+    """--lr_policy=reference: for_dataset; poly / cosine: the warm-up + decay schedules."""
     if FLAGS.lr_policy == "poly":
         return poly(FLAGS.peak_lr, FLAGS.warmup_steps, FLAGS.train_steps, FLAGS.poly_power, FLAGS.end_lr)
+    if FLAGS.lr_policy == "warmup_cosine":
+        return cosine(FLAGS.peak_lr, FLAGS.warmup_steps, FLAGS.train_steps, FLAGS.end_lr)
     return for_dataset(FLAGS.dataset, FLAGS.lr_schedule_scale)

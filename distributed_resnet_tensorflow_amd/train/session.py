@@ -81,7 +81,8 @@ class TrainingSession:
                  step_trial: bool = True, optimizer: str = "momentum", lars_eta: float = 0.001,
                  lars_eps: float = 1e-9, label_smoothing: float = 0.0, top_k: int = 0, ema_decay: float = 0.0,
                  ema_warmup: bool = True, mix: bool = False, clip_grad_norm: float = 0.0,
-                 skip_nonfinite_grads: bool = False):
+                 skip_nonfinite_grads: bool = False, adam_beta1: float = 0.9, adam_beta2: float = 0.999,
+                 adam_eps: float = 1e-6):
         self.cluster = cluster
         self.spec = spec
         self.device = torch.device(cluster.device)
@@ -90,7 +91,8 @@ class TrainingSession:
                            optimizer=optimizer, lars_eta=lars_eta, lars_eps=lars_eps,
                            label_smoothing=label_smoothing, top_k=top_k, ema_decay=ema_decay,
                            ema_warmup=ema_warmup, mix=mix, clip_grad_norm=clip_grad_norm,
-                           skip_nonfinite_grads=skip_nonfinite_grads)
+                           skip_nonfinite_grads=skip_nonfinite_grads, adam_beta1=adam_beta1, adam_beta2=adam_beta2,
+                           adam_eps=adam_eps)
         if self.ex.guarding and shard_optimizer:
             raise ValueError("clip_grad_norm / skip_nonfinite_grads need the gradient's global norm; a shard of the "
                              "sharded optimizer sees only part of it")
@@ -217,6 +219,9 @@ class TrainingSession:
             was = Saver.restore_meta(prefix)["ema_decay"]
             if was != self.ex.ema_decay:
                 log.warning("checkpoint was trained with ema_decay %g, continuing with %g", was, self.ex.ema_decay)
+            was = Saver.restore_meta(prefix)["optimizer"]
+            if was != self.ex.optimizer:
+                log.warning("checkpoint was trained with optimizer %s, continuing with %s", was, self.ex.optimizer)
         if self.engine is not None:
             self.engine.broadcast_parameters()
             if self.cluster.is_chief is False:
@@ -289,6 +294,7 @@ class TrainingSession:
         # (device memory like the LR: graph and plan replays read this step's warm-up value)
         self.ex.set_ema_decay(self.ex.P.global_step)
         self.cur_ema_decay = self.ex.ema_decay_at(self.ex.P.global_step)
+        self.ex.set_adam_step(self.ex.P.global_step)   # (Adam's bias corrections, likewise)
         if self.use_graph and not self.ex.check_nan:  # the debug checks synchronize: no capture
             if self._graph is None:  # warm-up = this real step
                 if self.engine is not None and self.engine.p2p is None:

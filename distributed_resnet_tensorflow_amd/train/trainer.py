@@ -54,6 +54,7 @@ def _meta(FLAGS, spec):
             "num_classes": spec.num_classes,
             "spec_name": spec.name,
             "optimizer": FLAGS.optimizer, "eta": FLAGS.lars_eta, "eps": FLAGS.lars_eps,
+            "adam_beta1": FLAGS.adam_beta1, "adam_beta2": FLAGS.adam_beta2, "adam_eps": FLAGS.adam_epsilon,
             "label_smoothing": FLAGS.label_smoothing, "ema_decay": FLAGS.ema_decay,
             "mixup_alpha": FLAGS.mixup_alpha, "cutmix_alpha": FLAGS.cutmix_alpha,
             "clip_grad_norm": FLAGS.clip_grad_norm, "skip_nonfinite_grads": FLAGS.skip_nonfinite_grads,
@@ -142,7 +143,8 @@ def train(FLAGS, cluster=None):
                            lars_eta=FLAGS.lars_eta, lars_eps=FLAGS.lars_eps,
                            label_smoothing=FLAGS.label_smoothing, top_k=FLAGS.top_k, ema_decay=FLAGS.ema_decay,
                            ema_warmup=FLAGS.ema_warmup, mix=mixing(FLAGS), clip_grad_norm=FLAGS.clip_grad_norm,
-                           skip_nonfinite_grads=FLAGS.skip_nonfinite_grads)
+                           skip_nonfinite_grads=FLAGS.skip_nonfinite_grads, adam_beta1=FLAGS.adam_beta1,
+                           adam_beta2=FLAGS.adam_beta2, adam_eps=FLAGS.adam_epsilon)
     feeder = make_feeder(FLAGS, sess.ex, cluster, True, sess.data_state)
     is_imagenet = FLAGS.dataset == "imagenet"
     hooks = [LoggingHook(FLAGS.log_every_n_steps, FLAGS.batch_size * cluster.world,
