@@ -209,6 +209,12 @@ def validate(fv: "FlagValues") -> None:
             raise FlagsError("--imagenet_preprocessing=inception / --color_jitter are not supported by --model=lrnet")
     if fv.color_jitter > 0 and fv.imagenet_preprocessing != "inception":
         raise FlagsError("--color_jitter > 0 needs --imagenet_preprocessing=inception")
+    if fv.model == "resnext":
+        if fv.dataset != "imagenet":
+            raise FlagsError(f"--model=resnext is an ImageNet network: not supported with --dataset={fv.dataset}")
+        if fv.cardinality < 2 or fv.width_per_group < 1:
+            raise FlagsError(f"--model=resnext needs --cardinality >= 2 and --width_per_group >= 1, got "
+                             f"{fv.cardinality!r}, {fv.width_per_group!r}")
 
 
 FLAGS = FlagValues()
@@ -276,8 +282,10 @@ def define_reference_flags(flag_values: FlagValues = FLAGS, **defaults) -> FlagV
     I("hidden_units", 100, "LRNet hidden units.", fv)
     # ---- framework flags ----
     I("resnet_size", None, "ResNet depth (reference hard-codes 50): CIFAR 6n+2, ImageNet 18..200.", fv)
-    S("model", "resnet", "resnet | wide_resnet | lrnet.", fv)
+    S("model", "resnet", "resnet | wide_resnet | resnext | lrnet.", fv)
     I("width_multiplier", 2, "Bottleneck width multiplier for --model=wide_resnet (WRN-50-2).", fv)
+    I("cardinality", 32, "Groups of the bottleneck 3x3 conv for --model=resnext (ResNeXt-50 32x4d: 32).", fv)
+    I("width_per_group", 4, "Stage-1 channels per group for --model=resnext (doubles every stage; 32x4d: 4).", fv)
     S("precision", "bf16", "Compute precision of the GPU path (bf16 activations, fp32 master).", fv)
     B("synthetic_data", False, "Use synthetic data of the dataset's shape (benchmarks).", fv)
     I("save_checkpoint_secs", 60, "Checkpoint period in seconds (reference: 60).", fv)

@@ -24,8 +24,8 @@ def _conv(x, w_hwio, c: Conv):
         pb = (k - 1) // 2
         pe = k - 1 - pb
         x = F.pad(x, (pb, pe, pb, pe))
-        return F.conv2d(x, w, stride=s)
-    return F.conv2d(x, w, stride=1, padding=(k - 1) // 2)  # SAME for odd k
+        return F.conv2d(x, w, stride=s, groups=c.groups)
+    return F.conv2d(x, w, stride=1, padding=(k - 1) // 2, groups=c.groups)  # SAME for odd k
 
 
 def _bn_relu(x, bn: BN, p, state, training):

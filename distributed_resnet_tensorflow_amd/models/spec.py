@@ -35,10 +35,13 @@ class Conv:
     k: int
     stride: int
     cin_store: int = 0  # channels as stored/computed (stem input padded 3 -> 8); 0 = cin
+    groups: int = 1     # grouped conv (ResNeXt): output group g reads input channels [g*cin/groups, ...)
 
     def __post_init__(self):
         if not self.cin_store:
             self.cin_store = self.cin
+        if self.groups < 1 or self.cin % self.groups or self.cout % self.groups:
+            raise ValueError(f"{self.name}: groups={self.groups} must divide cin={self.cin} and cout={self.cout}")
 
     @property
     def pad(self) -> int:
@@ -53,7 +56,7 @@ class Conv:
 
     @property
     def params(self) -> int:
-        return self.k * self.k * self.cin * self.cout
+        return self.k * self.k * (self.cin // self.groups) * self.cout
 
 
 @dataclass
@@ -101,7 +104,7 @@ class NetSpec:
         out = []
 
         def conv(c: Conv):
-            out.append((f"{c.name}/kernel", (c.k, c.k, c.cin, c.cout), "conv", c))
+            out.append((f"{c.name}/kernel", (c.k, c.k, c.cin // c.groups, c.cout), "conv", c))
 
         def bn(b: BN):
             out.append((f"{b.name}/gamma", (b.c,), "gamma", b))
@@ -180,7 +183,7 @@ class _Namer:
 
 
 def _stage(spec: NetSpec, nm: _Namer, kind: str, stage: int, filters: int, blocks: int, stride: int,
-           in_c: int, hw: int, width: int = 1) -> tuple[int, int]:
+           in_c: int, hw: int, width: int = 1, groups: int = 1, width_per_group: int = 64) -> tuple[int, int]:
     out_c = filters * 4 if kind == "bottleneck" else filters
     for i in range(blocks):
         s = stride if i == 0 else 1
@@ -193,10 +196,11 @@ def _stage(spec: NetSpec, nm: _Namer, kind: str, stage: int, filters: int, block
             c2 = Conv(nm.next_conv(), filters, filters, 3, 1)
             convs, bns = [c1, c2], [b2]
         else:
-            mid = filters * width
+            # ResNeXt: `groups` paths of width_per_group * 2^(stage-1) channels through the 3x3 conv
+            mid = filters * width if groups == 1 else groups * width_per_group * 2 ** (stage - 1)
             c1 = Conv(nm.next_conv(), in_c, mid, 1, 1)
             b2 = BN(nm.next_bn(), mid)
-            c2 = Conv(nm.next_conv(), mid, mid, 3, s)
+            c2 = Conv(nm.next_conv(), mid, mid, 3, s, groups=groups)
             b3 = BN(nm.next_bn(), mid)
             c3 = Conv(nm.next_conv(), mid, out_c, 1, 1)
             convs, bns = [c1, c2, c3], [b2, b3]
@@ -233,31 +237,45 @@ IMAGENET_SIZES = {
 
 
 def imagenet_resnet_v2(resnet_size: int = 50, num_classes: int = 1001, width: int = 1,
-                       image_size: int = 224) -> NetSpec:
-    """imagenet_resnet_v2 (reference resnet_model_official.py:281-366); width=2 -> WRN-50-2 (extension)."""
+                       image_size: int = 224, groups: int = 1, width_per_group: int = 64) -> NetSpec:
+    """imagenet_resnet_v2 (reference resnet_model_official.py:281-366); width=2 -> WRN-50-2 (extension);
+    groups > 1 -> ResNeXt (extension): the bottleneck's 3x3 conv is grouped, its width in stage s is
+    groups * width_per_group * 2^(s-1) (32x4d: 128 / 256 / 512 / 1024), the block output stays filters * 4."""
     if resnet_size not in IMAGENET_SIZES:
         raise ValueError(f"Not a valid resnet_size: {resnet_size}")
     kind, layers = IMAGENET_SIZES[resnet_size]
+    if groups < 1 or width_per_group < 1:
+        raise ValueError(f"groups and width_per_group must be >= 1, got {groups}, {width_per_group}")
+    if groups > 1 and (kind != "bottleneck" or width != 1):
+        raise ValueError("ResNeXt (groups > 1) needs a bottleneck resnet_size (50, 101, 152, 200) and width 1")
     nm = _Namer()
     stem = Conv(nm.next_conv(), 3, 64, 7, 2, cin_store=8)
     stem_hw = stem.out_hw(image_size)
     pool_hw = (stem_hw + 1) // 2  # max_pooling2d(3, 2, 'SAME')
     tag = f"wide_resnet{resnet_size}_{width}" if width != 1 else f"imagenet_resnet{resnet_size}_v2"
+    if groups > 1:
+        tag = f"resnext{resnet_size}_{groups}x{width_per_group}d"
     spec = NetSpec(tag, "imagenet", num_classes, image_size, 3, stem, stem_hw, True, pool_hw)
     c, hw = 64, pool_hw
     for stage, (f, s) in enumerate(((64, 1), (128, 2), (256, 2), (512, 2)), start=1):
-        c, hw = _stage(spec, nm, kind, stage, f, layers[stage - 1], s, c, hw, width=width)
+        c, hw = _stage(spec, nm, kind, stage, f, layers[stage - 1], s, c, hw, width=width, groups=groups,
+                       width_per_group=width_per_group)
     spec.final_bn = BN(nm.next_bn(), c)
     spec.final_hw, spec.final_c = hw, c
     return spec
 
 
 def build_spec(dataset: str, resnet_size: int | None = None, model: str = "resnet", width: int = 1,
-               num_classes: int | None = None) -> NetSpec:
+               num_classes: int | None = None, cardinality: int = 32, width_per_group: int = 4) -> NetSpec:
     """Network selection of the reference ResNet wrapper (resnet_model.py:71-74, size fixed to 50
     there; `--resnet_size` makes it selectable here). cifar100 is supported."""
     if model == "wide_resnet":
         width = max(width, 2)
+    if model == "resnext":
+        if dataset != "imagenet":
+            raise ValueError("model=resnext is an ImageNet network (bottleneck blocks)")
+        return imagenet_resnet_v2(resnet_size or 50, num_classes or 1001, groups=cardinality,
+                                  width_per_group=width_per_group)
     if dataset in ("cifar10", "cifar100", "cifar"):
         nc = num_classes or (100 if dataset == "cifar100" else 10)
         return cifar_resnet_v2(resnet_size or 50, nc)

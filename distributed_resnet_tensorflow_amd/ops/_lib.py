@@ -77,6 +77,22 @@ class DrnConvWgradArgs(ctypes.Structure):
     ]
 
 
+class DrnGconvArgs(ctypes.Structure):
+    """Mirror of csrc/kernels/conv_group.hip `struct DrnGconvArgs` (grouped 3x3 conv; the entry points
+    fill every field after stats_rep)."""
+    _fields_ = [
+        ("x", c_p), ("w", c_p), ("y", c_p), ("dy", c_p), ("dx", c_p), ("dw", c_p), ("stats", c_p), ("ws", c_p),
+        ("ws_elems", c_i64),
+        ("N", c_int), ("H", c_int), ("W", c_int), ("P", c_int), ("Q", c_int), ("C", c_int), ("cg", c_int),
+        ("stride", c_int), ("stats_rep", c_int),
+        ("cg_shift", c_int), ("th", c_int), ("tw", c_int), ("tiles_y", c_int), ("tiles_x", c_int),
+        ("ntiles", c_int), ("tpw", c_int), ("ih", c_int), ("iw", c_int), ("oth", c_int), ("otw", c_int),
+        ("in_h", c_int), ("in_w", c_int), ("out_h", c_int), ("out_w", c_int), ("in_bytes", c_int),
+        ("fd_tw", DrnFastDiv), ("fd_iw", DrnFastDiv), ("fd_otw", DrnFastDiv), ("fd_tx", DrnFastDiv),
+        ("fd_txy", DrnFastDiv),
+    ]
+
+
 class DrnConvCfgInfo(ctypes.Structure):
     """Mirror of csrc/include/drn_conv.h `struct DrnConvCfgInfo` (drn_conv_cfg_info)."""
     _fields_ = [(n, c_int) for n in ("kind", "bp", "bc", "waves_p", "ns", "nw", "bk", "nh", "il", "ks")]
@@ -102,6 +118,12 @@ _SIGS = {
     "drn_conv_glds_default_cfg": ([ctypes.POINTER(DrnConvFwdArgs)], c_int),
     "drn_conv_wgrad": ([ctypes.POINTER(DrnConvWgradArgs), c_p], c_int),
     "drn_conv_wgrad2": ([ctypes.POINTER(DrnConvWgradArgs), c_p, c_int, c_p], c_int),
+    # grouped 3x3 conv (conv_group.hip): forward (+ statistics), data gradient, weight gradient
+    "drn_gconv_fwd": ([ctypes.POINTER(DrnGconvArgs), c_p], c_int),
+    "drn_gconv_dgrad": ([ctypes.POINTER(DrnGconvArgs), c_p], c_int),
+    "drn_gconv_wgrad": ([ctypes.POINTER(DrnGconvArgs), c_p], c_int),
+    "drn_gconv_wgrad_ws_elems": ([ctypes.POINTER(DrnGconvArgs)], c_i64),
+    "drn_gconv_args_size": ([], c_int),
     "drn_splitk_reduce": ([c_p, c_p, c_i64, c_int, c_f, c_int, c_p], c_int),
     "drn_bn_stats": ([c_p, c_p, c_int, c_int, c_int, c_int, c_p], c_int),
     "drn_bn_finalize": ([c_p, c_int, c_int, c_f, c_p, c_p, c_f, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_p], c_int),
@@ -238,7 +260,7 @@ def lib():
             fn.argtypes = args
             fn.restype = res
         for name, st in (("drn_bn_fin_size", DrnBnFin), ("drn_conv_args_size", DrnConvFwdArgs),
-                         ("drn_wgrad_args_size", DrnConvWgradArgs)):
+                         ("drn_wgrad_args_size", DrnConvWgradArgs), ("drn_gconv_args_size", DrnGconvArgs)):
             if getattr(h, name)() != ctypes.sizeof(st):
                 raise KernelLibraryError(f"{st.__name__} layout mismatch between Python and {LIB_PATH.name}")
         _check_stamp(h)

@@ -790,6 +790,76 @@ class HipBackend(_Common):
             a = args_for(tgt, atomic, ms)
         self._wgrad_full(a, ns, out, st)
 
+    # -- grouped 3x3 conv (csrc/kernels/conv_group.hip) -------------------------------------------
+    GCONV_WIDTHS = (4, 8, 16, 32)
+
+    @classmethod
+    def gconv_check(cls, x_shape, y_shape, w_shape, stride: int):
+        """Raises unless input x_shape [N,H,W,C], output y_shape [N,P,Q,K] and weights / gradient w_shape
+        [K,3,3,cg] are inside the grouped kernels' domain (needs no device)."""
+        N, H, W, C = x_shape
+        N2, P, Q, K = y_shape
+        Kw, R, S, cg = w_shape
+        if not (R == S == 3 and C == K == Kw and N == N2 and C % 32 == 0 and cg in cls.GCONV_WIDTHS
+                and C % cg == 0 and stride in (1, 2) and P == (H - 1) // stride + 1 and Q == (W - 1) // stride + 1):
+            raise ValueError(f"grouped conv outside the HIP kernels' domain (3x3, stride 1 or 2, C == K, C % 32 == 0, "
+                             f"group width in {cls.GCONV_WIDTHS}): x {tuple(x_shape)}, y {tuple(y_shape)}, "
+                             f"w {tuple(w_shape)}, stride {stride}")
+
+    def gconv_args(self, x_shape, y_shape, w_shape, stride: int):
+        """Argument block of a grouped 3x3 conv (shapes as gconv_check, which it applies)."""
+        self.gconv_check(x_shape, y_shape, w_shape, stride)
+        N, H, W, C = x_shape
+        _, P, Q, _ = y_shape
+        cg = w_shape[3]
+        a = _lib.DrnGconvArgs()
+        a.N, a.H, a.W, a.P, a.Q, a.C, a.cg, a.stride = N, H, W, P, Q, C, cg, stride
+        return a
+
+    @staticmethod
+    def _gconv_tensors(*ts):
+        for t in ts:
+            if not (t.is_contiguous() and t.dtype == torch.bfloat16 and t.data_ptr() % 16 == 0):
+                raise ValueError("grouped conv: tensors must be contiguous, bf16 and 16-byte aligned")
+
+    def gconv_fwd(self, x, w, y, stride, stats=None):
+        """y = conv(x, w) with groups = C / w.shape[3]; optional BN statistics of the stored y."""
+        a = self.gconv_args(x.shape, y.shape, w.shape, stride)
+        self._gconv_tensors(x, w, y)
+        a.x, a.w, a.y = x.data_ptr(), w.data_ptr(), y.data_ptr()
+        if stats is not None:
+            assert stats.numel() % (2 * a.C) == 0 and stats.dtype == torch.float32, \
+                "stats accumulator must be fp32 [rep][2][K]"
+            a.stats, a.stats_rep = stats.data_ptr(), stats.numel() // (2 * a.C)
+        _lib.check(self.L.drn_gconv_fwd(ctypes.byref(a), self.stream()), "drn_gconv_fwd")
+
+    def gconv_dgrad(self, dy, w, dx, stride):
+        """dx = data gradient of gconv_fwd (from the forward weights; every element of dx is written)."""
+        a = self.gconv_args(dx.shape, dy.shape, w.shape, stride)
+        self._gconv_tensors(dy, w, dx)
+        a.dy, a.w, a.dx = dy.data_ptr(), w.data_ptr(), dx.data_ptr()
+        _lib.check(self.L.drn_gconv_dgrad(ctypes.byref(a), self.stream()), "drn_gconv_dgrad")
+
+    def gconv_wgrad_ws_elems(self, x_shape, y_shape, w_shape, stride):
+        n = self.L.drn_gconv_wgrad_ws_elems(ctypes.byref(self.gconv_args(x_shape, y_shape, w_shape, stride)))
+        if n < 0:
+            raise ValueError(f"grouped weight gradient: unsupported geometry {tuple(x_shape)} -> {tuple(y_shape)}")
+        return int(n)
+
+    def gconv_wgrad(self, x, dy, out, stride, ws=None):
+        """out[K,3,3,cg] (fp32) = weight gradient of gconv_fwd; bitwise reproducible (per-workgroup
+        cells in ws summed in a fixed order, no atomics)."""
+        a = self.gconv_args(x.shape, dy.shape, out.shape, stride)
+        self._gconv_tensors(x, dy)
+        if not (out.is_contiguous() and out.dtype == torch.float32 and out.data_ptr() % 16 == 0):
+            raise ValueError("grouped weight gradient: out must be contiguous, fp32 and 16-byte aligned")
+        a.x, a.dy, a.dw = x.data_ptr(), dy.data_ptr(), out.data_ptr()
+        if ws is not None:
+            if ws.dtype != torch.float32 or ws.data_ptr() % 16:
+                raise ValueError("grouped weight gradient: the workspace must be fp32 and 16-byte aligned")
+            a.ws, a.ws_elems = ws.data_ptr(), ws.numel()
+        _lib.check(self.L.drn_gconv_wgrad(ctypes.byref(a), self.stream()), "drn_gconv_wgrad")
+
     # -- batch norm -----------------------------------------------------------------------------
     @staticmethod
     def bn_rows_per_block(M, C):
@@ -1355,6 +1425,37 @@ class RefBackend(_Common):
         _, P, Q, _ = dy.shape
         xc = _pad_for(_pre(x, in_bn, relu_in).permute(0, 3, 1, 2), P, Q, R, S, g)
         dw = torch.nn.grad.conv2d_weight(xc, (K, C, R, S), dy.to(_DT[0]).permute(0, 3, 1, 2), stride=g.stride)
+        out.copy_(dw.permute(0, 2, 3, 1))
+
+    # grouped 3x3 conv: the HIP contract (weights [K,3,3,cg], leading pad 1) for any group width
+    def gconv_fwd(self, x, w, y, stride, stats=None):
+        K, R, S, cg = w.shape
+        g = ConvGeom(stride, (R - 1) // 2, (S - 1) // 2, 1)
+        xc = _pad_for(x.to(_DT[0]).permute(0, 3, 1, 2), y.shape[1], y.shape[2], R, S, g)
+        y.copy_(F.conv2d(xc, w.to(_DT[0]).permute(0, 3, 1, 2), stride=stride, groups=K // cg).permute(0, 2, 3, 1))
+        if stats is not None:
+            yy = y.to(_DT[0]).reshape(-1, K)
+            stats.view(-1)[:K].add_(yy.sum(0))
+            stats.view(-1)[K:2 * K].add_((yy * yy).sum(0))
+
+    def gconv_dgrad(self, dy, w, dx, stride):
+        K, R, S, cg = w.shape
+        N, H, W, C = dx.shape
+        g = ConvGeom(stride, (R - 1) // 2, (S - 1) // 2, 1)
+        shape = _pad_for(dx.new_zeros(1, 1, H, W), dy.shape[1], dy.shape[2], R, S, g).shape
+        d = torch.nn.grad.conv2d_input((N, C, shape[2], shape[3]), w.to(_DT[0]).permute(0, 3, 1, 2),
+                                       dy.to(_DT[0]).permute(0, 3, 1, 2), stride=stride, groups=K // cg)
+        dx.copy_(d[:, :, g.pad_h:g.pad_h + H, g.pad_w:g.pad_w + W].permute(0, 2, 3, 1))
+
+    def gconv_wgrad_ws_elems(self, x_shape, y_shape, w_shape, stride):
+        return 0
+
+    def gconv_wgrad(self, x, dy, out, stride, ws=None):
+        K, R, S, cg = out.shape
+        g = ConvGeom(stride, (R - 1) // 2, (S - 1) // 2, 1)
+        xc = _pad_for(x.to(_DT[0]).permute(0, 3, 1, 2), dy.shape[1], dy.shape[2], R, S, g)
+        dw = torch.nn.grad.conv2d_weight(xc, (K, cg, R, S), dy.to(_DT[0]).permute(0, 3, 1, 2), stride=stride,
+                                         groups=K // cg)
         out.copy_(dw.permute(0, 2, 3, 1))
 
     def bn_stats(self, x, part):

@@ -91,7 +91,15 @@ def _stamp_object() -> Path:
     return obj
 
 
+# Extra hipcc flags of single translation units. conv_group.hip is built with the packed-fp32 VALU
+# forms off: the MI355X pool this library is checked on asks that of HIP code added to it. Without
+# the flag hipcc emits 8 v_pk_add_f32 / v_pk_mul_f32 in that file (the statistics sums); with it
+# their scalar forms, at no measurable cost. The older translation units are built as before.
+SOURCE_FLAGS = {"conv_group.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+
+
 def _compile(src: Path, extra: list[str], obj_dir: Optional[Path] = None, include: Path = INCLUDE) -> Path:
+    extra = SOURCE_FLAGS.get(src.name, []) + list(extra)
     obj = (obj_dir or OBJ_DIR) / (src.stem + ".o")
     hdr = max((h.stat().st_mtime for h in include.glob("*.h")), default=0.0)
     if obj.exists() and obj.stat().st_mtime >= max(src.stat().st_mtime, hdr):

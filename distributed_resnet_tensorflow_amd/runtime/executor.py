@@ -110,6 +110,20 @@ class Executor:
                  skip_nonfinite_grads: bool = False, adam_beta1: float = 0.9, adam_beta2: float = 0.999,
                  adam_eps: float = 1e-6):
         self.spec, self.N, self.be = spec, batch, backend
+        if backend.name == "hip":
+            # grouped convs outside the HIP kernels' domain (e.g. ResNeXt 32x8d's 64-wide groups in stage 4)
+            # are refused here, before anything is allocated; the reference backend takes any
+            for blk in spec.blocks:
+                hw = blk.in_hw
+                for c in blk.convs:
+                    if c.groups > 1:
+                        try:
+                            backend.gconv_check((batch, hw, hw, c.cin), (batch, c.out_hw(hw), c.out_hw(hw), c.cout),
+                                                (c.cout, c.k, c.k, c.cin // c.groups), c.stride)
+                        except ValueError as e:
+                            raise ValueError(f"{spec.name}: {c.name} ({c.groups} groups of {c.cin // c.groups} "
+                                             f"channels) cannot run on the HIP backend: {e}") from None
+                    hw = c.out_hw(hw)
         # clip_grad_norm = c > 0: the gradient the optimizer reads is scaled by c / max(norm, c), norm
         # its global L2 norm (grad_scale included; TF's clip_by_global_norm). skip_nonfinite_grads: a
         # step whose norm is NaN / Inf changes no weight, momentum, bf16 copy, EMA or trust ratio.
@@ -299,7 +313,11 @@ class Executor:
         phases = []
         full = True
         K, R, C = c.cout, c.k, c.cin_store
-        if c is not self.spec.stem:
+        if c.groups > 1:
+            # grouped 3x3 (ResNeXt): csrc/kernels/conv_group.hip gathers its data-gradient fragments from
+            # the forward weights, so there is no flipped copy to refresh; one launch writes all of dX
+            pass
+        elif c is not self.spec.stem:
             if c.stride == 1:
                 wt_descs.append(tflip_desc(s.offset, wt_off, K, R, R, C))
                 phases.append(DgradPhase((C, R, R, K), wt_off, dgrad_geom(g, R, R), None))
@@ -492,6 +510,10 @@ class Executor:
             ins = [x] + h_list
             for op, xin in zip(convs, ins):
                 o_hw = op.conv.out_hw(xin.shape[1])
+                if op.conv.groups > 1:
+                    ws_need = max(ws_need, be.gconv_wgrad_ws_elems(xin.shape, (N, o_hw, o_hw, op.conv.cout),
+                                                                   op.dw.shape, op.conv.stride))
+                    continue
                 ws_need = max(ws_need, be.wgrad_ws_elems(N * o_hw * o_hw, op.conv.cout, op.conv.k, op.conv.k,
                                                          op.conv.cin_store))
             if proj is not None:
@@ -509,8 +531,10 @@ class Executor:
 
                 def fusable(c):
                     return c.k == 1 and -(-c.cout // 128) < self.mat_tiles
-                if self.bn_policy == "all" or (self.bn_policy == "1x1" and big and
-                                               not all(fusable(c) for c in consumers)):
+                # (the grouped convs have no BN prologue: their input is materialised on every backend)
+                grouped = any(c.groups > 1 for c in consumers)
+                if grouped or self.bn_policy == "all" or (self.bn_policy == "1x1" and big and
+                                                          not all(fusable(c) for c in consumers)):
                     b.act = self._act(*b.src.shape)
         for b in [b for bp in self.blocks for b in bp.bn] + [self.final_bn]:
             b.bacc, b.bG = self._stats_for(b.rows, b.bn.c)
@@ -777,6 +801,10 @@ class Executor:
                 res = bp.sc if bp.proj is not None else bp.x
                 be.conv_fwd(xin, op.w, bp.out, op.geom, in_bn=pro, residual=res, in_fin=fin,
                             stats=bp.out_stats if train else None)
+            elif op.conv.groups > 1:
+                assert pro is None, "a grouped conv reads a materialised BatchNorm output"
+                be.gconv_fwd(xin, op.w, bp.hs[i], op.conv.stride, stats=bn[i + 1].stats if train else None)
+                self._bn_fwd(bn[i + 1], train)
             else:
                 be.conv_fwd(xin, op.w, bp.hs[i], op.geom, in_bn=pro, in_fin=fin,
                             stats=bn[i + 1].stats if train else None)
@@ -932,14 +960,21 @@ class Executor:
         self._reported = True
 
     # -- weight gradients on the side stream ---------------------------------------------------------
-    def _wgrad(self, x, dy, dw, geom, in_bn=None, dy_buf=None, post=None, pre=None):
+    def _wgrad(self, x, dy, dw, geom, in_bn=None, dy_buf=None, post=None, pre=None, grouped=False):
         """Weight gradient into dw (on the side stream when enabled); pre() / post() run right
         before / after it, on the same stream (the stem's max-pool backward producing dy; the
         packed stem mapping its gradient back to the checkpoint layout)."""
+        if grouped:
+            def wgrad():
+                assert in_bn is None, "a grouped conv reads a materialised BatchNorm output"
+                self.be.gconv_wgrad(x, dy, dw, geom.stride, ws=self.wgrad_ws)
+        else:
+            def wgrad():
+                self.be.conv_wgrad(x, dy, dw, geom, in_bn=in_bn, ws=self.wgrad_ws)
         if self.side is None:
             if pre is not None:
                 pre()
-            self.be.conv_wgrad(x, dy, dw, geom, in_bn=in_bn, ws=self.wgrad_ws)
+            wgrad()
             if post is not None:
                 post()
             return
@@ -948,7 +983,7 @@ class Executor:
         with torch.cuda.stream(self.side):
             if pre is not None:
                 pre()
-            self.be.conv_wgrad(x, dy, dw, geom, in_bn=in_bn, ws=self.wgrad_ws)
+            wgrad()
             if post is not None:
                 post()
         if dy_buf is not None:                           # the main stream must not overwrite dy early
@@ -997,6 +1032,10 @@ class Executor:
         covering every dx element) the epilogue also performs that BN's backward reduction."""
         # a single-phase strided data gradient (1x1 stride-2 projection) writes the zeros of the
         # other phases from its own epilogue instead of a separate clearing pass over dx
+        if op.conv.groups > 1:
+            assert not accumulate and bn is None, "grouped data gradient: plain output only"
+            self.be.gconv_dgrad(dy, op.w, dx, op.conv.stride)
+            return
         fill = self.out_fill and not accumulate and not op.full_cover and len(op.dg) == 1 \
             and op.dg[0].out_map is not None and bn is None
         if not accumulate and not op.full_cover and not fill:
@@ -1024,13 +1063,14 @@ class Executor:
             tgt_k = self._take(bufs, (cur, dy_k))
             tgt = bufs[tgt_k]
             a_in, pro = (b.act, None) if b.act is not None else (b.src, b.ss)
-            self._wgrad(a_in, dy, op.dw, op.geom, in_bn=pro, dy_buf=dy_buf)
+            self._wgrad(a_in, dy, op.dw, op.geom, in_bn=pro, dy_buf=dy_buf, grouped=op.conv.groups > 1)
             if i == 0 and bp.proj is not None:
                 self._wgrad(a_in, d_out, bp.proj.dw, bp.proj.geom, in_bn=pro, dy_buf=bufs[cur])
             self._claim(tgt)
             da = self._view(tgt, xin)        # d relu(bn(xin))
             add = None
-            fuse = self.fuse_bn_bwd and op.full_cover
+            # (a grouped conv's data gradient carries no BN reduction: bn_bwd_reduce + the apply)
+            fuse = self.fuse_bn_bwd and op.full_cover and op.conv.groups == 1
             if i == 0 and bp.proj is not None:
                 # the projection's data gradient first, the main conv's accumulating one last so
                 # that its (full-cover, stride-1) epilogue can carry the fused BN reduction

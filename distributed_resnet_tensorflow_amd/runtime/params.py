@@ -63,7 +63,7 @@ class ParamStore:
         off = 0
         for name, tf_shape, kind, owner in spec.trainable_variables():
             if kind == "conv":
-                shape = (owner.cout, owner.k, owner.k, owner.cin_store)
+                shape = (owner.cout, owner.k, owner.k, owner.cin_store // owner.groups)
             elif kind == "dense_w":
                 shape = (tf_shape[1], tf_shape[0])
             else:
@@ -127,10 +127,11 @@ class ParamStore:
             v = host[s.offset:s.offset + s.numel].view(s.shape)
             if s.kind == "conv":
                 c = s.owner
-                fan_in = c.k * c.k * c.cin
+                cin = c.cin // c.groups   # (a grouped conv's kernel and fan-in are per group)
+                fan_in = c.k * c.k * cin
                 std = math.sqrt(1.0 / fan_in) / 0.87962566103423978
-                w = _trunc_normal((c.cout, c.k, c.k, c.cin), std, gen)
-                v[..., :c.cin] = w
+                w = _trunc_normal((c.cout, c.k, c.k, cin), std, gen)
+                v[..., :cin] = w
             elif s.kind == "gamma":
                 v.fill_(1.0)
             elif s.kind == "dense_w":
@@ -177,7 +178,7 @@ class ParamStore:
         v = self.view(self.master if buf is None else buf, name).detach().cpu().to(dtype)
         if s.kind == "conv":
             c = s.owner
-            return v[..., :c.cin].permute(1, 2, 3, 0).contiguous()  # KRSC -> HWIO
+            return v[..., :c.cin // c.groups].permute(1, 2, 3, 0).contiguous()  # KRSC -> HWIO
         if s.kind == "dense_w":
             return v.t().contiguous()
         return v.clone()
@@ -189,7 +190,7 @@ class ParamStore:
         if s.kind == "conv":
             c = s.owner
             t = torch.zeros(s.shape, dtype=self.dtype)
-            t[..., :c.cin] = value.permute(3, 0, 1, 2)
+            t[..., :c.cin // c.groups] = value.permute(3, 0, 1, 2)
             dst.copy_(t)
         elif s.kind == "dense_w":
             dst.copy_(value.t())

@@ -45,7 +45,8 @@ def model_spec_from_flags(FLAGS):
     # --width_multiplier only shapes --model=wide_resnet; --model=resnet is always the reference's
     # ResNet-v2 (resnet_model.py:74, resnet_imagenet_main.py:266-272: 25,551,401 params at size 50)
     width = FLAGS.width_multiplier if model == "wide_resnet" else 1
-    return build_spec(ds, FLAGS.resnet_size, model=model, width=width)
+    return build_spec(ds, FLAGS.resnet_size, model=model, width=width, cardinality=FLAGS.cardinality,
+                      width_per_group=FLAGS.width_per_group)
 
 
 def _meta(FLAGS, spec):
@@ -53,6 +54,9 @@ def _meta(FLAGS, spec):
             "width_multiplier": FLAGS.width_multiplier if FLAGS.model == "wide_resnet" else 1,
             "num_classes": spec.num_classes,
             "spec_name": spec.name,
+            # ResNeXt only (absent = a plain ResNet)
+            **({"cardinality": FLAGS.cardinality, "width_per_group": FLAGS.width_per_group}
+               if FLAGS.model == "resnext" else {}),
             "optimizer": FLAGS.optimizer, "eta": FLAGS.lars_eta, "eps": FLAGS.lars_eps,
             "adam_beta1": FLAGS.adam_beta1, "adam_beta2": FLAGS.adam_beta2, "adam_eps": FLAGS.adam_epsilon,
             "label_smoothing": FLAGS.label_smoothing, "ema_decay": FLAGS.ema_decay,
