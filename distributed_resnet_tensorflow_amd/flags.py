@@ -217,6 +217,12 @@ def validate(fv: "FlagValues") -> None:
                              f"{fv.cardinality!r}, {fv.width_per_group!r}")
 
 
+    if fv.se_ratio not in (0, 4, 8, 16):
+        raise FlagsError(f"--se_ratio must be 0 (off), 4, 8 or 16, got {fv.se_ratio!r}")
+    if fv.se_ratio and fv.model == "lrnet":
+        raise FlagsError("--se_ratio is not supported by --model=lrnet")
+
+
 FLAGS = FlagValues()
 
 
@@ -286,6 +292,8 @@ def define_reference_flags(flag_values: FlagValues = FLAGS, **defaults) -> FlagV
     I("width_multiplier", 2, "Bottleneck width multiplier for --model=wide_resnet (WRN-50-2).", fv)
     I("cardinality", 32, "Groups of the bottleneck 3x3 conv for --model=resnext (ResNeXt-50 32x4d: 32).", fv)
     I("width_per_group", 4, "Stage-1 channels per group for --model=resnext (doubles every stage; 32x4d: 4).", fv)
+    I("se_ratio", 0, "Squeeze-and-Excitation reduction ratio (4, 8 or 16) gating every block's residual branch; "
+      "0 = off. Any --model but lrnet.", fv)
     S("precision", "bf16", "Compute precision of the GPU path (bf16 activations, fp32 master).", fv)
     B("synthetic_data", False, "Use synthetic data of the dataset's shape (benchmarks).", fv)
     I("save_checkpoint_secs", 60, "Checkpoint period in seconds (reference: 60).", fv)

@@ -61,6 +61,11 @@ def forward(spec: NetSpec, p: Dict[str, torch.Tensor], state: Dict[str, tuple], 
         h = _conv(a, p[f"{blk.convs[0].name}/kernel"], blk.convs[0])
         for b, c in zip(blk.bns, blk.convs[1:]):
             h = _conv(_bn_relu(h, b, p, state, training), p[f"{c.name}/kernel"], c)
+        if blk.se is not None:   # the gate on the residual branch: squeeze, two dense layers, excite
+            e = blk.se.name
+            z = h.mean(dim=(2, 3))
+            hid = torch.relu(z @ p[f"{e}/reduce/kernel"] + p[f"{e}/reduce/bias"])
+            h = h * torch.sigmoid(hid @ p[f"{e}/expand/kernel"] + p[f"{e}/expand/bias"])[:, :, None, None]
         x = h + shortcut
     x = _bn_relu(x, spec.final_bn, p, state, training)
     x = x.mean(dim=(2, 3))

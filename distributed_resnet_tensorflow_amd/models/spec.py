@@ -66,6 +66,15 @@ class BN:
 
 
 @dataclass
+class SE:
+    """Squeeze-and-Excitation gate on a block's residual branch (extension, SE-PreResNet placement):
+    out = shortcut + sigmoid(relu(mean_hw(u) W1 + b1) W2 + b2) * u, u the last main-path conv's output."""
+    name: str   # TF scope "squeeze_excite_3" -> variables ".../reduce/kernel", ".../expand/bias", ...
+    c: int
+    hidden: int
+
+
+@dataclass
 class Block:
     kind: str                 # "basic" | "bottleneck"
     stage: int
@@ -79,6 +88,7 @@ class Block:
     proj: Optional[Conv]
     convs: List[Conv]         # basic: [conv3x3(stride), conv3x3]; bottleneck: [1x1, 3x3(stride), 1x1]
     bns: List[BN]             # BNs preceding convs[1:], i.e. bn2 (and bn3)
+    se: Optional[SE] = None   # gate on the residual branch (se_ratio > 0)
 
 
 @dataclass
@@ -119,6 +129,12 @@ class NetSpec:
             for b, c in zip(blk.bns, blk.convs[1:]):
                 bn(b)
                 conv(c)
+            if blk.se is not None:
+                e = blk.se
+                out.append((f"{e.name}/reduce/kernel", (e.c, e.hidden), "se_w", e))
+                out.append((f"{e.name}/reduce/bias", (e.hidden,), "se_b", e))
+                out.append((f"{e.name}/expand/kernel", (e.hidden, e.c), "se_w", e))
+                out.append((f"{e.name}/expand/bias", (e.c,), "se_b", e))
         bn(self.final_bn)
         out.append((f"{self.dense_name}/kernel", (self.final_c, self.num_classes), "dense_w", None))
         out.append((f"{self.dense_name}/bias", (self.num_classes,), "dense_b", None))
@@ -161,6 +177,8 @@ class NetSpec:
             for c in blk.convs:
                 h = c.out_hw(h)
                 fl += 2 * c.params * h * h
+            if blk.se is not None:   # the two gate layers (the squeeze and the excite are not multiply-adds)
+                fl += 2 * 2 * blk.se.c * blk.se.hidden
         fl += 2 * self.final_c * self.num_classes
         del hw
         return fl
@@ -170,6 +188,7 @@ class _Namer:
     def __init__(self):
         self.conv = 0
         self.bn = 0
+        self.se = 0
 
     def next_conv(self) -> str:
         n = "conv2d" if self.conv == 0 else f"conv2d_{self.conv}"
@@ -182,8 +201,23 @@ class _Namer:
         return n
 
 
+    def next_se(self) -> str:
+        n = "squeeze_excite" if self.se == 0 else f"squeeze_excite_{self.se}"
+        self.se += 1
+        return n
+
+
+SE_RATIOS = (0, 4, 8, 16)
+
+
+def _check_se_ratio(se_ratio: int):
+    if se_ratio not in SE_RATIOS:
+        raise ValueError(f"se_ratio must be one of {SE_RATIOS}, got {se_ratio!r}")
+
+
 def _stage(spec: NetSpec, nm: _Namer, kind: str, stage: int, filters: int, blocks: int, stride: int,
-           in_c: int, hw: int, width: int = 1, groups: int = 1, width_per_group: int = 64) -> tuple[int, int]:
+           in_c: int, hw: int, width: int = 1, groups: int = 1, width_per_group: int = 64,
+           se_ratio: int = 0) -> tuple[int, int]:
     out_c = filters * 4 if kind == "bottleneck" else filters
     for i in range(blocks):
         s = stride if i == 0 else 1
@@ -205,22 +239,26 @@ def _stage(spec: NetSpec, nm: _Namer, kind: str, stage: int, filters: int, block
             c3 = Conv(nm.next_conv(), mid, out_c, 1, 1)
             convs, bns = [c1, c2, c3], [b2, b3]
         out_hw = convs[0].out_hw(hw) if kind == "basic" else convs[1].out_hw(hw)
-        spec.blocks.append(Block(kind, stage, i, in_c, out_c, hw, out_hw, s, bn1, proj, convs, bns))
+        se = SE(nm.next_se(), out_c, max(out_c // se_ratio, 8)) if se_ratio else None
+        spec.blocks.append(Block(kind, stage, i, in_c, out_c, hw, out_hw, s, bn1, proj, convs, bns, se))
         in_c, hw = out_c, out_hw
     return in_c, hw
 
 
-def cifar_resnet_v2(resnet_size: int = 50, num_classes: int = 10) -> NetSpec:
-    """cifar10_resnet_v2_generator (reference resnet_model_official.py:217-278)."""
+def cifar_resnet_v2(resnet_size: int = 50, num_classes: int = 10, se_ratio: int = 0) -> NetSpec:
+    """cifar10_resnet_v2_generator (reference resnet_model_official.py:217-278); se_ratio > 0 ->
+    every block gated by Squeeze-and-Excitation (extension)."""
     if resnet_size % 6 != 2:
         raise ValueError(f"resnet_size must be 6n + 2: {resnet_size}")
+    _check_se_ratio(se_ratio)
     n = (resnet_size - 2) // 6
     nm = _Namer()
     stem = Conv(nm.next_conv(), 3, 16, 3, 1, cin_store=8)
-    spec = NetSpec(f"cifar_resnet{resnet_size}_v2", "cifar", num_classes, 32, 3, stem, 32, False, 32)
+    spec = NetSpec(("se_" if se_ratio else "") + f"cifar_resnet{resnet_size}_v2", "cifar", num_classes, 32, 3, stem,
+                   32, False, 32)
     c, hw = 16, 32
     for stage, (f, s) in enumerate(((16, 1), (32, 2), (64, 2)), start=1):
-        c, hw = _stage(spec, nm, "basic", stage, f, n, s, c, hw)
+        c, hw = _stage(spec, nm, "basic", stage, f, n, s, c, hw, se_ratio=se_ratio)
     spec.final_bn = BN(nm.next_bn(), c)
     spec.final_hw, spec.final_c = hw, c
     return spec
@@ -237,10 +275,12 @@ IMAGENET_SIZES = {
 
 
 def imagenet_resnet_v2(resnet_size: int = 50, num_classes: int = 1001, width: int = 1,
-                       image_size: int = 224, groups: int = 1, width_per_group: int = 64) -> NetSpec:
+                       image_size: int = 224, groups: int = 1, width_per_group: int = 64,
+                       se_ratio: int = 0) -> NetSpec:
     """imagenet_resnet_v2 (reference resnet_model_official.py:281-366); width=2 -> WRN-50-2 (extension);
     groups > 1 -> ResNeXt (extension): the bottleneck's 3x3 conv is grouped, its width in stage s is
-    groups * width_per_group * 2^(s-1) (32x4d: 128 / 256 / 512 / 1024), the block output stays filters * 4."""
+    groups * width_per_group * 2^(s-1) (32x4d: 128 / 256 / 512 / 1024), the block output stays filters * 4.
+    se_ratio > 0 -> every block gated by Squeeze-and-Excitation, hidden width max(C / se_ratio, 8) (extension)."""
     if resnet_size not in IMAGENET_SIZES:
         raise ValueError(f"Not a valid resnet_size: {resnet_size}")
     kind, layers = IMAGENET_SIZES[resnet_size]
@@ -248,6 +288,7 @@ def imagenet_resnet_v2(resnet_size: int = 50, num_classes: int = 1001, width: in
         raise ValueError(f"groups and width_per_group must be >= 1, got {groups}, {width_per_group}")
     if groups > 1 and (kind != "bottleneck" or width != 1):
         raise ValueError("ResNeXt (groups > 1) needs a bottleneck resnet_size (50, 101, 152, 200) and width 1")
+    _check_se_ratio(se_ratio)
     nm = _Namer()
     stem = Conv(nm.next_conv(), 3, 64, 7, 2, cin_store=8)
     stem_hw = stem.out_hw(image_size)
@@ -255,18 +296,21 @@ def imagenet_resnet_v2(resnet_size: int = 50, num_classes: int = 1001, width: in
     tag = f"wide_resnet{resnet_size}_{width}" if width != 1 else f"imagenet_resnet{resnet_size}_v2"
     if groups > 1:
         tag = f"resnext{resnet_size}_{groups}x{width_per_group}d"
+    if se_ratio:
+        tag = "se_" + tag
     spec = NetSpec(tag, "imagenet", num_classes, image_size, 3, stem, stem_hw, True, pool_hw)
     c, hw = 64, pool_hw
     for stage, (f, s) in enumerate(((64, 1), (128, 2), (256, 2), (512, 2)), start=1):
         c, hw = _stage(spec, nm, kind, stage, f, layers[stage - 1], s, c, hw, width=width, groups=groups,
-                       width_per_group=width_per_group)
+                       width_per_group=width_per_group, se_ratio=se_ratio)
     spec.final_bn = BN(nm.next_bn(), c)
     spec.final_hw, spec.final_c = hw, c
     return spec
 
 
 def build_spec(dataset: str, resnet_size: int | None = None, model: str = "resnet", width: int = 1,
-               num_classes: int | None = None, cardinality: int = 32, width_per_group: int = 4) -> NetSpec:
+               num_classes: int | None = None, cardinality: int = 32, width_per_group: int = 4,
+               se_ratio: int = 0) -> NetSpec:
     """Network selection of the reference ResNet wrapper (resnet_model.py:71-74, size fixed to 50
     there; `--resnet_size` makes it selectable here). cifar100 is supported."""
     if model == "wide_resnet":
@@ -275,10 +319,10 @@ def build_spec(dataset: str, resnet_size: int | None = None, model: str = "resne
         if dataset != "imagenet":
             raise ValueError("model=resnext is an ImageNet network (bottleneck blocks)")
         return imagenet_resnet_v2(resnet_size or 50, num_classes or 1001, groups=cardinality,
-                                  width_per_group=width_per_group)
+                                  width_per_group=width_per_group, se_ratio=se_ratio)
     if dataset in ("cifar10", "cifar100", "cifar"):
         nc = num_classes or (100 if dataset == "cifar100" else 10)
-        return cifar_resnet_v2(resnet_size or 50, nc)
+        return cifar_resnet_v2(resnet_size or 50, nc, se_ratio=se_ratio)
     if dataset == "imagenet":
-        return imagenet_resnet_v2(resnet_size or 50, num_classes or 1001, width=width)
+        return imagenet_resnet_v2(resnet_size or 50, num_classes or 1001, width=width, se_ratio=se_ratio)
     raise ValueError(f"unknown dataset {dataset}")

@@ -93,6 +93,15 @@ class DrnGconvArgs(ctypes.Structure):
     ]
 
 
+class DrnSeArgs(ctypes.Structure):
+    """Mirror of csrc/kernels/se.hip `struct DrnSeArgs` (Squeeze-and-Excitation; the entry points fill
+    every field after stats_rep)."""
+    _fields_ = [(n, c_p) for n in ("x", "y", "out", "cells", "w1", "b1", "w2", "b2", "z", "h", "s", "dl2", "dh",
+                                   "dzs", "dw1", "db1", "dw2", "db2", "stats")] + \
+               [(n, c_int) for n in ("N", "HW", "C", "Cr", "S", "stats_rep", "pps", "slab", "cpw", "planes")] + \
+               [("inv_hw", c_f), ("pad_", c_int)]
+
+
 class DrnConvCfgInfo(ctypes.Structure):
     """Mirror of csrc/include/drn_conv.h `struct DrnConvCfgInfo` (drn_conv_cfg_info)."""
     _fields_ = [(n, c_int) for n in ("kind", "bp", "bc", "waves_p", "ns", "nw", "bk", "nh", "il", "ks")]
@@ -124,6 +133,11 @@ _SIGS = {
     "drn_gconv_wgrad": ([ctypes.POINTER(DrnGconvArgs), c_p], c_int),
     "drn_gconv_wgrad_ws_elems": ([ctypes.POINTER(DrnGconvArgs)], c_i64),
     "drn_gconv_args_size": ([], c_int),
+    # Squeeze-and-Excitation (se.hip): squeeze, gate forward, excite, gate backward / weight gradient, scale
+    **{f"drn_se_{k}": ([ctypes.POINTER(DrnSeArgs), c_p], c_int)
+       for k in ("squeeze", "gate_fwd", "excite", "gate_bwd", "gate_wgrad", "scale_bwd")},
+    "drn_se_splits": ([c_int, c_int, c_int], c_int),
+    "drn_se_args_size": ([], c_int),
     "drn_splitk_reduce": ([c_p, c_p, c_i64, c_int, c_f, c_int, c_p], c_int),
     "drn_bn_stats": ([c_p, c_p, c_int, c_int, c_int, c_int, c_p], c_int),
     "drn_bn_finalize": ([c_p, c_int, c_int, c_f, c_p, c_p, c_f, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_p], c_int),
@@ -260,7 +274,8 @@ def lib():
             fn.argtypes = args
             fn.restype = res
         for name, st in (("drn_bn_fin_size", DrnBnFin), ("drn_conv_args_size", DrnConvFwdArgs),
-                         ("drn_wgrad_args_size", DrnConvWgradArgs), ("drn_gconv_args_size", DrnGconvArgs)):
+                         ("drn_wgrad_args_size", DrnConvWgradArgs), ("drn_gconv_args_size", DrnGconvArgs),
+                         ("drn_se_args_size", DrnSeArgs)):
             if getattr(h, name)() != ctypes.sizeof(st):
                 raise KernelLibraryError(f"{st.__name__} layout mismatch between Python and {LIB_PATH.name}")
         _check_stamp(h)

@@ -16,6 +16,7 @@ Op contract (NHWC activations, KRSC conv weights, fp32 statistics):
   mix_pairs(src, dst, table)                                 Mixup / CutMix of a batch with its reversal
   box_preprocess(packed, desc, out, mean, std, jitter)       Inception-style input: box resample, colour jitter
   grad_guard(g, grad_scale, clip, guard, skip_in, ws, rec)   global-norm clip + non-finite step guard
+  se_squeeze / se_gate_fwd / se_excite / se_gate_bwd / se_gate_wgrad / se_scale_bwd   Squeeze-and-Excitation gate
 where pre(x) = relu(x * scale + shift) when in_bn = (scale, shift) is given.
 """
 from __future__ import annotations
@@ -84,7 +85,7 @@ def tflip_table(descs):
 LARS_SLOT = np.dtype([("offset", "<i8"), ("numel", "<i4"), ("padded", "<i4"), ("adapt", "<i4"), ("pad_", "<i4"),
                       ("begin", "<i8")])  # mirror of sgd.hip `struct LarsSlot`
 LARS_CHUNK = 8192                         # elements per work chunk (sgd.hip LARS_CHUNK4 * 4)
-LARS_EXCLUDED = ("gamma", "beta", "dense_b")  # slot kinds whose trust ratio is fixed at 1
+LARS_EXCLUDED = ("gamma", "beta", "dense_b", "se_b")  # slot kinds whose trust ratio is fixed at 1
 
 
 class LarsTable:
@@ -860,6 +861,86 @@ class HipBackend(_Common):
             a.ws, a.ws_elems = ws.data_ptr(), ws.numel()
         _lib.check(self.L.drn_gconv_wgrad(ctypes.byref(a), self.stream()), "drn_gconv_wgrad")
 
+    # -- Squeeze-and-Excitation (csrc/kernels/se.hip) ---------------------------------------------
+    @staticmethod
+    def se_check(N: int, HW: int, C: int, Cr: int):
+        """Raises unless an SE gate of C channels and hidden width Cr is inside the kernels' domain (needs
+        no device)."""
+        if not (N >= 1 and HW >= 1 and 16 <= C <= 4096 and C % 16 == 0 and 8 <= Cr <= 1024 and Cr % 8 == 0):
+            raise ValueError(f"Squeeze-and-Excitation outside the HIP kernels' domain (C % 16 == 0, 16 <= C <= 4096, "
+                             f"hidden % 8 == 0, 8 <= hidden <= 1024): N {N}, HW {HW}, C {C}, hidden {Cr}")
+
+    def se_splits(self, N: int, HW: int, C: int) -> int:
+        """Pixel splits S of se_squeeze for this geometry: its cells are fp32 [N, S, C]."""
+        self.se_check(N, HW, C, 8)
+        return int(self.L.drn_se_splits(N, HW, C))
+
+    def _se_args(self, N, HW, C, Cr, **tensors):
+        """Argument block; tensors by field name: bf16 for x / y / out, fp32 for the rest, all contiguous
+        and 16-byte aligned."""
+        self.se_check(N, HW, C, Cr)
+        a = _lib.DrnSeArgs()
+        a.N, a.HW, a.C, a.Cr = N, HW, C, Cr
+        for k, t in tensors.items():
+            if t is None:
+                continue
+            want = torch.bfloat16 if k in ("x", "y", "out") else torch.float32
+            if not (t.is_contiguous() and t.dtype == want and t.data_ptr() % 16 == 0):
+                raise ValueError(f"Squeeze-and-Excitation: {k} must be contiguous, {want} and 16-byte aligned")
+            setattr(a, k, t.data_ptr())
+        return a
+
+    def _se_run(self, entry: str, a):
+        _lib.check(getattr(self.L, entry)(ctypes.byref(a), self.stream()), entry)
+
+    def se_squeeze(self, u, cells, g=None):
+        """cells[N, S, C] = per-split sums over the pixels of u (of g * u with g): S = se_splits."""
+        N, C = u.shape[0], u.shape[-1]
+        a = self._se_args(N, u.numel() // (N * C), C, 8, x=u, y=g, cells=cells)
+        a.S = cells.shape[1]
+        assert cells.shape == (N, a.S, C) and (g is None or g.shape == u.shape)
+        self._se_run("drn_se_squeeze", a)
+
+    def se_gate_fwd(self, cells, hw, w1, b1, w2, b2, z, h, s):
+        """z = sum_S cells / hw, h = relu(z w1 + b1), s = sigmoid(h w2 + b2) in one launch."""
+        N, S, C = cells.shape
+        a = self._se_args(N, hw, C, w1.shape[1], cells=cells, w1=w1, b1=b1, w2=w2, b2=b2, z=z, h=h, s=s)
+        a.S = S
+        assert w1.shape == (C, a.Cr) and w2.shape == (a.Cr, C) and s.shape == z.shape == (N, C) and h.shape == (N, a.Cr)
+        self._se_run("drn_se_gate_fwd", a)
+
+    def se_excite(self, u, shortcut, s, out, stats=None):
+        """out = bf16(shortcut + s * u); stats[R, 2, C] += sum, sum of squares of the stored out."""
+        N, C = u.shape[0], u.shape[-1]
+        a = self._se_args(N, u.numel() // (N * C), C, 8, x=u, y=shortcut, s=s, out=out, stats=stats)
+        assert shortcut.shape == u.shape == out.shape and s.shape == (N, C)
+        if stats is not None:
+            assert stats.numel() % (2 * C) == 0, "stats accumulator must be fp32 [rep][2][C]"
+            a.stats_rep = stats.numel() // (2 * C)
+        self._se_run("drn_se_excite", a)
+
+    def se_gate_bwd(self, cells, hw, w1, w2, h, s, dl2, dh, dzs):
+        """From the cells of g * u: dl2 = ds s (1 - s), dh = (dl2 w2^T) [h > 0], dzs = dh w1^T / hw."""
+        N, S, C = cells.shape
+        a = self._se_args(N, hw, C, w1.shape[1], cells=cells, w1=w1, w2=w2, h=h, s=s, dl2=dl2, dh=dh, dzs=dzs)
+        a.S = S
+        assert w1.shape == (C, a.Cr) and w2.shape == (a.Cr, C) and s.shape == dl2.shape == dzs.shape == (N, C) \
+            and h.shape == dh.shape == (N, a.Cr)
+        self._se_run("drn_se_gate_bwd", a)
+
+    def se_gate_wgrad(self, z, h, dl2, dh, dw1, db1, dw2, db2):
+        """dw1 = z^T dh, db1 = sum_n dh, dw2 = h^T dl2, db2 = sum_n dl2: one launch, samples in order."""
+        (N, C), Cr = z.shape, h.shape[1]
+        assert dw1.shape == (C, Cr) and dw2.shape == (Cr, C) and dl2.shape == (N, C) and dh.shape == (N, Cr)
+        self._se_run("drn_se_gate_wgrad", self._se_args(N, 1, C, Cr, z=z, h=h, dl2=dl2, dh=dh, dw1=dw1, db1=db1,
+                                                        dw2=dw2, db2=db2))
+
+    def se_scale_bwd(self, g, s, dzs, du):
+        """du = bf16(s * g + dzs), dzs broadcast over the pixels."""
+        N, C = g.shape[0], g.shape[-1]
+        assert du.shape == g.shape and s.shape == dzs.shape == (N, C)
+        self._se_run("drn_se_scale_bwd", self._se_args(N, g.numel() // (N * C), C, 8, x=g, s=s, dzs=dzs, out=du))
+
     # -- batch norm -----------------------------------------------------------------------------
     @staticmethod
     def bn_rows_per_block(M, C):
@@ -1457,6 +1538,43 @@ class RefBackend(_Common):
         dw = torch.nn.grad.conv2d_weight(xc, (K, cg, R, S), dy.to(_DT[0]).permute(0, 3, 1, 2), stride=stride,
                                          groups=K // cg)
         out.copy_(dw.permute(0, 2, 3, 1))
+
+    # Squeeze-and-Excitation: the HIP contract (ops named as csrc/kernels/se.hip's kernels), one split
+    def se_splits(self, N, HW, C):
+        return 1
+
+    def se_squeeze(self, u, cells, g=None):
+        N, C = u.shape[0], u.shape[-1]
+        t = u.to(_DT[0]) if g is None else u.to(_DT[0]) * g.to(_DT[0])
+        cells.zero_()
+        cells[:, 0].copy_(t.reshape(N, -1, C).sum(1))
+
+    def se_gate_fwd(self, cells, hw, w1, b1, w2, b2, z, h, s):
+        z.copy_(cells.sum(1) / hw)
+        h.copy_(torch.relu(z @ w1 + b1))
+        s.copy_(torch.sigmoid(h @ w2 + b2))
+
+    def se_excite(self, u, shortcut, s, out, stats=None):
+        C = u.shape[-1]
+        out.copy_(shortcut.to(_DT[0]) + s[:, None, None, :] * u.to(_DT[0]))   # (rounds where out is bf16)
+        if stats is not None:
+            yy = out.to(_DT[0]).reshape(-1, C)
+            stats.view(-1)[:C].add_(yy.sum(0))
+            stats.view(-1)[C:2 * C].add_((yy * yy).sum(0))
+
+    def se_gate_bwd(self, cells, hw, w1, w2, h, s, dl2, dh, dzs):
+        dl2.copy_(cells.sum(1) * s * (1 - s))
+        dh.copy_((dl2 @ w2.t()) * (h > 0))
+        dzs.copy_(dh @ w1.t() / hw)
+
+    def se_gate_wgrad(self, z, h, dl2, dh, dw1, db1, dw2, db2):
+        dw1.copy_(z.t() @ dh)
+        db1.copy_(dh.sum(0))
+        dw2.copy_(h.t() @ dl2)
+        db2.copy_(dl2.sum(0))
+
+    def se_scale_bwd(self, g, s, dzs, du):
+        du.copy_(s[:, None, None, :] * g.to(_DT[0]) + dzs[:, None, None, :])
 
     def bn_stats(self, x, part):
         C = x.shape[-1]

@@ -88,6 +88,29 @@ class ConvOp:
 
 
 @dataclass
+class SEState:
+    """Squeeze-and-Excitation gate of one block (csrc/kernels/se.hip): the fp32 masters and gradient
+    views of its four variables, the gated tensor u and the small fp32 tensors both passes keep."""
+    hw: int                  # pixels per sample of u
+    w1: torch.Tensor         # reduce/kernel [C, Cr]
+    b1: torch.Tensor
+    w2: torch.Tensor         # expand/kernel [Cr, C]
+    b2: torch.Tensor
+    dw1: torch.Tensor
+    db1: torch.Tensor
+    dw2: torch.Tensor
+    db2: torch.Tensor
+    u: torch.Tensor          # the last main-path conv's output (no shortcut)
+    cells: torch.Tensor      # squeeze cells [N, S, C]: of u forward, of d_out * u backward
+    z: torch.Tensor          # [N, C]
+    h: torch.Tensor          # [N, Cr]
+    s: torch.Tensor          # [N, C]
+    dl2: torch.Tensor        # [N, C]
+    dh: torch.Tensor         # [N, Cr]
+    dzs: torch.Tensor        # [N, C]  dz / hw
+
+
+@dataclass
 class BlockPlan:
     blk: Block
     x: torch.Tensor                 # block input (raw residual stream)
@@ -98,6 +121,7 @@ class BlockPlan:
     sc: Optional[torch.Tensor]      # projection output
     out: torch.Tensor               # block output
     grad_lo: int                    # lowest flat grad offset written by this block
+    se: Optional[SEState] = None    # the gate on the residual branch (SE blocks only)
 
 
 class Executor:
@@ -124,6 +148,11 @@ class Executor:
                             raise ValueError(f"{spec.name}: {c.name} ({c.groups} groups of {c.cin // c.groups} "
                                              f"channels) cannot run on the HIP backend: {e}") from None
                     hw = c.out_hw(hw)
+                if blk.se is not None:
+                    try:
+                        backend.se_check(batch, blk.out_hw * blk.out_hw, blk.se.c, blk.se.hidden)
+                    except ValueError as e:
+                        raise ValueError(f"{spec.name}: {blk.se.name} cannot run on the HIP backend: {e}") from None
         # clip_grad_norm = c > 0: the gradient the optimizer reads is scaled by c / max(norm, c), norm
         # its global L2 norm (grad_scale included; TF's clip_by_global_norm). skip_nonfinite_grads: a
         # step whose norm is NaN / Inf changes no weight, momentum, bf16 copy, EMA or trust ratio.
@@ -502,6 +531,15 @@ class Executor:
             grad_lo = min([o.grad_lo for o in convs] + ([proj.grad_lo] if proj else []) +
                           [self.P.by_name[f"{b.bn.name}/gamma"].offset for b in bns])
             bp = BlockPlan(blk, x, bns, convs, proj, h_list, sc, out, grad_lo)
+            if blk.se is not None:
+                e, P = blk.se, self.P
+                red, exp = f"{e.name}/reduce", f"{e.name}/expand"
+                S = be.se_splits(N, ohw * ohw, e.c)
+                bp.se = SEState(ohw * ohw, P.w(f"{red}/kernel"), P.w(f"{red}/bias"), P.w(f"{exp}/kernel"),
+                                P.w(f"{exp}/bias"), P.g(f"{red}/kernel"), P.g(f"{red}/bias"), P.g(f"{exp}/kernel"),
+                                P.g(f"{exp}/bias"), self._act(N, ohw, ohw, e.c), self._f32(N, S, e.c),
+                                self._f32(N, e.c), self._f32(N, e.hidden), self._f32(N, e.c), self._f32(N, e.c),
+                                self._f32(N, e.hidden), self._f32(N, e.c))
             self.blocks.append(bp)
             out_stats, out_G = self._stats_for(N * ohw * ohw, blk.out_c)
             bp.out_stats, bp.out_G = out_stats, out_G
@@ -577,6 +615,8 @@ class Executor:
             nbuf = max(6, min(self.GRAD_BUF_MAX, cap))
         else:
             nbuf = 6 if self.side is not None else 3
+        if any(bp.se is not None for bp in self.blocks):
+            nbuf += 1   # an SE block's backward holds d(out) AND the gated branch's gradient du
         self.g_bufs = [self._act(max_act) for _ in range(nbuf)]
         self.g_a, self.g_b, self.g_c = self.g_bufs[:3]
         self._lru: List[int] = []
@@ -797,7 +837,16 @@ class Executor:
         for i, op in enumerate(bp.convs):
             last = i == len(bp.convs) - 1
             xin, pro, fin = self._cin(bn[i])
-            if last:
+            if last and bp.se is not None:
+                # SE: the conv stores the branch u alone; squeeze -> gate -> excite, whose epilogue adds
+                # the shortcut and produces the next BatchNorm's statistics in the conv epilogue's place
+                e = bp.se
+                be.conv_fwd(xin, op.w, e.u, op.geom, in_bn=pro, in_fin=fin)
+                be.se_squeeze(e.u, e.cells)
+                be.se_gate_fwd(e.cells, e.hw, e.w1, e.b1, e.w2, e.b2, e.z, e.h, e.s)
+                be.se_excite(e.u, bp.sc if bp.proj is not None else bp.x, e.s, bp.out,
+                             stats=bp.out_stats if train else None)
+            elif last:
                 res = bp.sc if bp.proj is not None else bp.x
                 be.conv_fwd(xin, op.w, bp.out, op.geom, in_bn=pro, residual=res, in_fin=fin,
                             stats=bp.out_stats if train else None)
@@ -991,6 +1040,16 @@ class Executor:
             self._marks[self._wseq] = self.sched.record(self.side)
             self._pending[id(dy_buf)] = self._wseq
 
+    def _on_side(self, launch):
+        """A launch that only feeds the optimizer and reads no rotating gradient buffer (the SE gate's
+        weight gradients), after everything issued so far: on the side stream when enabled."""
+        if self.side is None:
+            launch()
+            return
+        self.sched.wait_stream(self.side, torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(self.side):
+            launch()
+
     def _claim(self, buf):
         """Before the main stream writes a rotating gradient buffer: wait for the side-stream
         weight gradient still reading it."""
@@ -1058,6 +1117,18 @@ class Executor:
         d_out = self._view(bufs[cur], bp.out)
         ins = [bp.x] + bp.hs                 # raw inputs of each main-path conv
         dy, dy_buf, dy_k = d_out, bufs[cur], cur
+        if bp.se is not None:
+            # the gated branch: ds = sum_hw d_out * u -> the gate's backward -> du = s * d_out + dz / hw is
+            # the last conv's dy; d_out itself stays live as the shortcut's gradient
+            e = bp.se
+            dy_k = self._take(bufs, (cur,))
+            dy_buf = bufs[dy_k]
+            self._claim(dy_buf)
+            dy = self._view(dy_buf, bp.out)
+            be.se_squeeze(e.u, e.cells, g=d_out)
+            be.se_gate_bwd(e.cells, e.hw, e.w1, e.w2, e.h, e.s, e.dl2, e.dh, e.dzs)
+            be.se_scale_bwd(d_out, e.s, e.dzs, dy)
+            self._on_side(lambda: be.se_gate_wgrad(e.z, e.h, e.dl2, e.dh, e.dw1, e.db1, e.dw2, e.db2))
         for i in reversed(range(len(bp.convs))):
             op, xin, b = bp.convs[i], ins[i], bp.bn[i]
             tgt_k = self._take(bufs, (cur, dy_k))

@@ -9,10 +9,13 @@ slices (parallel/engine.py) and the checkpoint a straight walk of the buffer (ck
 Internal layouts differ from TF's on-disk layouts and are converted only at checkpoint time:
   conv kernel   TF HWIO [k,k,cin,cout]   -> internal KRSC [cout,k,k,cin_store] (stem cin 3 -> 8)
   dense kernel  TF [in,out]              -> internal [out,in]
+  SE kernels    TF [in,out]              -> internal [in,out] (unchanged: csrc/kernels/se.hip reads the
+                                            fp32 masters row-major as stored; se_w / se_b slots)
 Initialisers follow TF1 defaults used by the reference (resnet_model_official.py:87-91,
 tf.layers.dense at :274/:343, batch_normalization at :45-48):
   conv: variance_scaling_initializer() = truncated normal, stddev sqrt(1/fan_in)/0.8796
   dense kernel: glorot_uniform; dense bias: zeros; BN gamma 1, beta 0, moving mean 0, var 1.
+  SE (extension): kernels glorot_uniform, biases zeros (tf.layers.dense defaults).
 """
 from __future__ import annotations
 
@@ -31,7 +34,7 @@ class Slot:
     name: str          # TF variable name
     tf_shape: tuple
     shape: tuple       # internal shape
-    kind: str          # conv | gamma | beta | dense_w | dense_b
+    kind: str          # conv | gamma | beta | dense_w | dense_b | se_w | se_b
     offset: int
     numel: int         # internal element count (incl. stem channel padding)
     owner: object = None
@@ -137,6 +140,9 @@ class ParamStore:
             elif s.kind == "dense_w":
                 fan_in, fan_out = s.tf_shape
                 lim = math.sqrt(6.0 / (fan_in + fan_out))
+                v.copy_(torch.rand(s.shape, generator=gen) * 2 * lim - lim)
+            elif s.kind == "se_w":
+                lim = math.sqrt(6.0 / sum(s.tf_shape))
                 v.copy_(torch.rand(s.shape, generator=gen) * 2 * lim - lim)
         self.master.copy_(host)
         self.seed_ema()

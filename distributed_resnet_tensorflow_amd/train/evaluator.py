@@ -54,6 +54,16 @@ def checkpoint_preprocessing(FLAGS, prefix: str) -> str:
     return was
 
 
+def checkpoint_se_ratio(FLAGS, prefix: str) -> int:
+    """The Squeeze-and-Excitation ratio the checkpoint was trained with (its .meta; absent = 0), so that
+    evaluation builds the network that was trained. An explicit --se_ratio that contradicts it is an error."""
+    was = Saver.restore_meta(prefix)["se_ratio"]
+    if "se_ratio" in FLAGS and FLAGS.is_present("se_ratio") and FLAGS.se_ratio != was:
+        raise FlagsError(f"--se_ratio={FLAGS.se_ratio} contradicts checkpoint {prefix}, whose .meta records "
+                         f"se_ratio={was} (drop the flag; the evaluator reads it from the .meta)")
+    return was
+
+
 def evaluate(FLAGS, eval_batch_size: int = 100, max_evals: int = -1):
     setup_logging(0)
     apply_thread_flags(FLAGS)
@@ -62,6 +72,9 @@ def evaluate(FLAGS, eval_batch_size: int = 100, max_evals: int = -1):
                          "undefined train() here, SURVEY Q1)")
     FLAGS.job_name = None
     cluster = cl.resolve(FLAGS, env={})
+    first = latest_checkpoint(FLAGS.log_root)
+    if first is not None and "se_ratio" in FLAGS:
+        FLAGS.se_ratio = checkpoint_se_ratio(FLAGS, first)
     spec = model_spec_from_flags(FLAGS)
     be = make_backend(cluster.device, getattr(FLAGS, "precision", "bf16"))
     top_k = int(getattr(FLAGS, "top_k", 0))
