@@ -192,4 +192,5 @@ class Saver:
         meta["adam_beta2"] = float(meta.get("adam_beta2", 0.999))
         meta["adam_eps"] = float(meta.get("adam_eps", 1e-6))
         meta["se_ratio"] = int(meta.get("se_ratio", 0))   # absent = no Squeeze-and-Excitation gate
+        meta["avg_down"] = bool(meta.get("avg_down", False))   # absent = strided projection shortcuts
         return meta

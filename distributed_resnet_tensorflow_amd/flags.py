@@ -221,6 +221,8 @@ def validate(fv: "FlagValues") -> None:
         raise FlagsError(f"--se_ratio must be 0 (off), 4, 8 or 16, got {fv.se_ratio!r}")
     if fv.se_ratio and fv.model == "lrnet":
         raise FlagsError("--se_ratio is not supported by --model=lrnet")
+    if fv.avg_down and fv.model == "lrnet":
+        raise FlagsError("--avg_down is not supported by --model=lrnet")
 
 
 FLAGS = FlagValues()
@@ -294,6 +296,8 @@ def define_reference_flags(flag_values: FlagValues = FLAGS, **defaults) -> FlagV
     I("width_per_group", 4, "Stage-1 channels per group for --model=resnext (doubles every stage; 32x4d: 4).", fv)
     I("se_ratio", 0, "Squeeze-and-Excitation reduction ratio (4, 8 or 16) gating every block's residual branch; "
       "0 = off. Any --model but lrnet.", fv)
+    B("avg_down", False, "ResNet-D shortcuts: every stride-2 projection becomes a 2x2 / 2 average pool + a 1x1 "
+      "stride-1 conv (same variables). Any --model but lrnet.", fv)
     S("precision", "bf16", "Compute precision of the GPU path (bf16 activations, fp32 master).", fv)
     B("synthetic_data", False, "Use synthetic data of the dataset's shape (benchmarks).", fv)
     I("save_checkpoint_secs", 60, "Checkpoint period in seconds (reference: 60).", fv)

@@ -56,8 +56,8 @@ def forward(spec: NetSpec, p: Dict[str, torch.Tensor], state: Dict[str, tuple], 
     for blk in spec.blocks:
         shortcut = x
         a = _bn_relu(x, blk.bn1, p, state, training)
-        if blk.proj is not None:
-            shortcut = _conv(a, p[f"{blk.proj.name}/kernel"], blk.proj)
+        if blk.proj is not None:   # (ResNet-D: on the 2x2 / 2 average-pooled activation)
+            shortcut = _conv(F.avg_pool2d(a, 2) if blk.avg_down else a, p[f"{blk.proj.name}/kernel"], blk.proj)
         h = _conv(a, p[f"{blk.convs[0].name}/kernel"], blk.convs[0])
         for b, c in zip(blk.bns, blk.convs[1:]):
             h = _conv(_bn_relu(h, b, p, state, training), p[f"{c.name}/kernel"], c)

@@ -89,6 +89,7 @@ class Block:
     convs: List[Conv]         # basic: [conv3x3(stride), conv3x3]; bottleneck: [1x1, 3x3(stride), 1x1]
     bns: List[BN]             # BNs preceding convs[1:], i.e. bn2 (and bn3)
     se: Optional[SE] = None   # gate on the residual branch (se_ratio > 0)
+    avg_down: bool = False    # ResNet-D shortcut: proj is 1x1 stride 1 on the 2x2 / 2 average-pooled input
 
 
 @dataclass
@@ -217,12 +218,16 @@ def _check_se_ratio(se_ratio: int):
 
 def _stage(spec: NetSpec, nm: _Namer, kind: str, stage: int, filters: int, blocks: int, stride: int,
            in_c: int, hw: int, width: int = 1, groups: int = 1, width_per_group: int = 64,
-           se_ratio: int = 0) -> tuple[int, int]:
+           se_ratio: int = 0, avg_down: bool = False) -> tuple[int, int]:
     out_c = filters * 4 if kind == "bottleneck" else filters
     for i in range(blocks):
         s = stride if i == 0 else 1
         bn1 = BN(nm.next_bn(), in_c)
-        proj = Conv(nm.next_conv(), in_c, out_c, 1, s) if i == 0 else None
+        # ResNet-D: a stride-2 projection pools 2x2 / 2 first and convolves at stride 1 (same variable)
+        pooled = avg_down and i == 0 and s == 2
+        if pooled and hw % 2:
+            raise ValueError(f"avg_down: stage {stage} downsamples an odd {hw} x {hw} input")
+        proj = Conv(nm.next_conv(), in_c, out_c, 1, 1 if pooled else s) if i == 0 else None
         convs, bns = [], []
         if kind == "basic":
             c1 = Conv(nm.next_conv(), in_c, filters, 3, s)
@@ -240,25 +245,26 @@ def _stage(spec: NetSpec, nm: _Namer, kind: str, stage: int, filters: int, block
             convs, bns = [c1, c2, c3], [b2, b3]
         out_hw = convs[0].out_hw(hw) if kind == "basic" else convs[1].out_hw(hw)
         se = SE(nm.next_se(), out_c, max(out_c // se_ratio, 8)) if se_ratio else None
-        spec.blocks.append(Block(kind, stage, i, in_c, out_c, hw, out_hw, s, bn1, proj, convs, bns, se))
+        spec.blocks.append(Block(kind, stage, i, in_c, out_c, hw, out_hw, s, bn1, proj, convs, bns, se, pooled))
         in_c, hw = out_c, out_hw
     return in_c, hw
 
 
-def cifar_resnet_v2(resnet_size: int = 50, num_classes: int = 10, se_ratio: int = 0) -> NetSpec:
+def cifar_resnet_v2(resnet_size: int = 50, num_classes: int = 10, se_ratio: int = 0,
+                    avg_down: bool = False) -> NetSpec:
     """cifar10_resnet_v2_generator (reference resnet_model_official.py:217-278); se_ratio > 0 ->
-    every block gated by Squeeze-and-Excitation (extension)."""
+    every block gated by Squeeze-and-Excitation (extension); avg_down -> ResNet-D shortcuts (extension)."""
     if resnet_size % 6 != 2:
         raise ValueError(f"resnet_size must be 6n + 2: {resnet_size}")
     _check_se_ratio(se_ratio)
     n = (resnet_size - 2) // 6
     nm = _Namer()
     stem = Conv(nm.next_conv(), 3, 16, 3, 1, cin_store=8)
-    spec = NetSpec(("se_" if se_ratio else "") + f"cifar_resnet{resnet_size}_v2", "cifar", num_classes, 32, 3, stem,
-                   32, False, 32)
+    spec = NetSpec(("se_" if se_ratio else "") + f"cifar_resnet{resnet_size}_v2" + ("_avgdown" if avg_down else ""),
+                   "cifar", num_classes, 32, 3, stem, 32, False, 32)
     c, hw = 16, 32
     for stage, (f, s) in enumerate(((16, 1), (32, 2), (64, 2)), start=1):
-        c, hw = _stage(spec, nm, "basic", stage, f, n, s, c, hw, se_ratio=se_ratio)
+        c, hw = _stage(spec, nm, "basic", stage, f, n, s, c, hw, se_ratio=se_ratio, avg_down=avg_down)
     spec.final_bn = BN(nm.next_bn(), c)
     spec.final_hw, spec.final_c = hw, c
     return spec
@@ -276,11 +282,13 @@ IMAGENET_SIZES = {
 
 def imagenet_resnet_v2(resnet_size: int = 50, num_classes: int = 1001, width: int = 1,
                        image_size: int = 224, groups: int = 1, width_per_group: int = 64,
-                       se_ratio: int = 0) -> NetSpec:
+                       se_ratio: int = 0, avg_down: bool = False) -> NetSpec:
     """imagenet_resnet_v2 (reference resnet_model_official.py:281-366); width=2 -> WRN-50-2 (extension);
     groups > 1 -> ResNeXt (extension): the bottleneck's 3x3 conv is grouped, its width in stage s is
     groups * width_per_group * 2^(s-1) (32x4d: 128 / 256 / 512 / 1024), the block output stays filters * 4.
-    se_ratio > 0 -> every block gated by Squeeze-and-Excitation, hidden width max(C / se_ratio, 8) (extension)."""
+    se_ratio > 0 -> every block gated by Squeeze-and-Excitation, hidden width max(C / se_ratio, 8) (extension).
+    avg_down -> ResNet-D shortcuts (extension): every stride-2 projection becomes a 2x2 / 2 average pool + a 1x1
+    stride-1 conv (Block.avg_down); variable names and shapes are unchanged."""
     if resnet_size not in IMAGENET_SIZES:
         raise ValueError(f"Not a valid resnet_size: {resnet_size}")
     kind, layers = IMAGENET_SIZES[resnet_size]
@@ -298,11 +306,13 @@ def imagenet_resnet_v2(resnet_size: int = 50, num_classes: int = 1001, width: in
         tag = f"resnext{resnet_size}_{groups}x{width_per_group}d"
     if se_ratio:
         tag = "se_" + tag
+    if avg_down:
+        tag += "_avgdown"
     spec = NetSpec(tag, "imagenet", num_classes, image_size, 3, stem, stem_hw, True, pool_hw)
     c, hw = 64, pool_hw
     for stage, (f, s) in enumerate(((64, 1), (128, 2), (256, 2), (512, 2)), start=1):
         c, hw = _stage(spec, nm, kind, stage, f, layers[stage - 1], s, c, hw, width=width, groups=groups,
-                       width_per_group=width_per_group, se_ratio=se_ratio)
+                       width_per_group=width_per_group, se_ratio=se_ratio, avg_down=avg_down)
     spec.final_bn = BN(nm.next_bn(), c)
     spec.final_hw, spec.final_c = hw, c
     return spec
@@ -310,7 +320,7 @@ def imagenet_resnet_v2(resnet_size: int = 50, num_classes: int = 1001, width: in
 
 def build_spec(dataset: str, resnet_size: int | None = None, model: str = "resnet", width: int = 1,
                num_classes: int | None = None, cardinality: int = 32, width_per_group: int = 4,
-               se_ratio: int = 0) -> NetSpec:
+               se_ratio: int = 0, avg_down: bool = False) -> NetSpec:
     """Network selection of the reference ResNet wrapper (resnet_model.py:71-74, size fixed to 50
     there; `--resnet_size` makes it selectable here). cifar100 is supported."""
     if model == "wide_resnet":
@@ -319,10 +329,11 @@ def build_spec(dataset: str, resnet_size: int | None = None, model: str = "resne
         if dataset != "imagenet":
             raise ValueError("model=resnext is an ImageNet network (bottleneck blocks)")
         return imagenet_resnet_v2(resnet_size or 50, num_classes or 1001, groups=cardinality,
-                                  width_per_group=width_per_group, se_ratio=se_ratio)
+                                  width_per_group=width_per_group, se_ratio=se_ratio, avg_down=avg_down)
     if dataset in ("cifar10", "cifar100", "cifar"):
         nc = num_classes or (100 if dataset == "cifar100" else 10)
-        return cifar_resnet_v2(resnet_size or 50, nc, se_ratio=se_ratio)
+        return cifar_resnet_v2(resnet_size or 50, nc, se_ratio=se_ratio, avg_down=avg_down)
     if dataset == "imagenet":
-        return imagenet_resnet_v2(resnet_size or 50, num_classes or 1001, width=width, se_ratio=se_ratio)
+        return imagenet_resnet_v2(resnet_size or 50, num_classes or 1001, width=width, se_ratio=se_ratio,
+                                  avg_down=avg_down)
     raise ValueError(f"unknown dataset {dataset}")

@@ -102,6 +102,13 @@ class DrnSeArgs(ctypes.Structure):
                [("inv_hw", c_f), ("pad_", c_int)]
 
 
+class DrnPoolProjArgs(ctypes.Structure):
+    """Mirror of csrc/kernels/pool_proj.hip `struct DrnPoolProjArgs` (ResNet-D pooled projection; the
+    entry points fill every field after Cout)."""
+    _fields_ = [(n, c_p) for n in ("x", "w", "scale", "shift", "sc", "ap", "dy", "da")] + \
+               [(n, c_int) for n in ("N", "H", "W", "Cin", "Cout", "P", "Q", "M", "K", "NC", "ncb")]
+
+
 class DrnConvCfgInfo(ctypes.Structure):
     """Mirror of csrc/include/drn_conv.h `struct DrnConvCfgInfo` (drn_conv_cfg_info)."""
     _fields_ = [(n, c_int) for n in ("kind", "bp", "bc", "waves_p", "ns", "nw", "bk", "nh", "il", "ks")]
@@ -138,6 +145,10 @@ _SIGS = {
        for k in ("squeeze", "gate_fwd", "excite", "gate_bwd", "gate_wgrad", "scale_bwd")},
     "drn_se_splits": ([c_int, c_int, c_int], c_int),
     "drn_se_args_size": ([], c_int),
+    # ResNet-D pooled projection (pool_proj.hip): forward (+ the pooled stash), data gradient
+    "drn_pool_proj_fwd": ([ctypes.POINTER(DrnPoolProjArgs), c_p], c_int),
+    "drn_pool_proj_dgrad": ([ctypes.POINTER(DrnPoolProjArgs), c_p], c_int),
+    "drn_pool_proj_args_size": ([], c_int),
     "drn_splitk_reduce": ([c_p, c_p, c_i64, c_int, c_f, c_int, c_p], c_int),
     "drn_bn_stats": ([c_p, c_p, c_int, c_int, c_int, c_int, c_p], c_int),
     "drn_bn_finalize": ([c_p, c_int, c_int, c_f, c_p, c_p, c_f, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_p], c_int),
@@ -275,7 +286,7 @@ def lib():
             fn.restype = res
         for name, st in (("drn_bn_fin_size", DrnBnFin), ("drn_conv_args_size", DrnConvFwdArgs),
                          ("drn_wgrad_args_size", DrnConvWgradArgs), ("drn_gconv_args_size", DrnGconvArgs),
-                         ("drn_se_args_size", DrnSeArgs)):
+                         ("drn_se_args_size", DrnSeArgs), ("drn_pool_proj_args_size", DrnPoolProjArgs)):
             if getattr(h, name)() != ctypes.sizeof(st):
                 raise KernelLibraryError(f"{st.__name__} layout mismatch between Python and {LIB_PATH.name}")
         _check_stamp(h)

@@ -861,6 +861,47 @@ class HipBackend(_Common):
             a.ws, a.ws_elems = ws.data_ptr(), ws.numel()
         _lib.check(self.L.drn_gconv_wgrad(ctypes.byref(a), self.stream()), "drn_gconv_wgrad")
 
+    # -- ResNet-D pooled projection (csrc/kernels/pool_proj.hip) -----------------------------------
+    @staticmethod
+    def pool_proj_check(x_shape, sc_shape):
+        """Raises unless input x_shape [N,H,W,Cin] and output sc_shape [N,H/2,W/2,Cout] are inside the pooled
+        projection kernels' domain (needs no device)."""
+        N, H, W, C = x_shape
+        N2, P, Q, K = sc_shape
+        if not (N == N2 >= 1 and H >= 2 and W >= 2 and H % 2 == 0 and W % 2 == 0 and (P, Q) == (H // 2, W // 2)
+                and C >= 8 and K >= 8 and C % 8 == 0 and K % 8 == 0):
+            raise ValueError(f"pooled projection outside the HIP kernels' domain (H and W even, Cin % 8 == 0, "
+                             f"Cout % 8 == 0): x {tuple(x_shape)}, sc {tuple(sc_shape)}")
+
+    def _pool_proj_args(self, x_shape, sc_shape, **tensors):
+        """Argument block; tensors by field name: fp32 for scale / shift, bf16 for the rest, all contiguous
+        and 16-byte aligned."""
+        self.pool_proj_check(x_shape, sc_shape)
+        a = _lib.DrnPoolProjArgs()
+        a.N, a.H, a.W, a.Cin, a.Cout = x_shape[0], x_shape[1], x_shape[2], x_shape[3], sc_shape[3]
+        for k, t in tensors.items():
+            want = torch.float32 if k in ("scale", "shift") else torch.bfloat16
+            if not (t.is_contiguous() and t.dtype == want and t.data_ptr() % 16 == 0):
+                raise ValueError(f"pooled projection: {k} must be contiguous, {want} and 16-byte aligned")
+            setattr(a, k, t.data_ptr())
+        return a
+
+    def pool_proj_fwd(self, x, w, sc, ap, in_bn=None):
+        """ap = bf16(avgpool2x2(a)), sc = conv1x1(ap, w): a = x, or relu(scale * x + shift) (each term
+        rounded to bf16) with in_bn = (scale, shift), which must be published. w is [Cout,1,1,Cin]."""
+        assert w.shape == (sc.shape[3], 1, 1, x.shape[3]) and ap.shape == sc.shape[:3] + x.shape[3:]
+        bn = {} if in_bn is None else {"scale": in_bn[0], "shift": in_bn[1]}
+        assert all(t.numel() == x.shape[3] for t in bn.values())
+        a = self._pool_proj_args(x.shape, sc.shape, x=x, w=w, sc=sc, ap=ap, **bn)
+        _lib.check(self.L.drn_pool_proj_fwd(ctypes.byref(a), self.stream()), "drn_pool_proj_fwd")
+
+    def pool_proj_dgrad(self, d_out, w, da):
+        """da[n, 2p+i, 2q+j] = bf16(0.25 * d_out[n, p, q] W) for i, j in {0, 1}: every element of da is
+        written. w is the data-gradient copy of the weights, [Cin,1,1,Cout]."""
+        assert w.shape == (da.shape[3], 1, 1, d_out.shape[3])
+        a = self._pool_proj_args(da.shape, d_out.shape, dy=d_out, w=w, da=da)
+        _lib.check(self.L.drn_pool_proj_dgrad(ctypes.byref(a), self.stream()), "drn_pool_proj_dgrad")
+
     # -- Squeeze-and-Excitation (csrc/kernels/se.hip) ---------------------------------------------
     @staticmethod
     def se_check(N: int, HW: int, C: int, Cr: int):
@@ -1538,6 +1579,18 @@ class RefBackend(_Common):
         dw = torch.nn.grad.conv2d_weight(xc, (K, cg, R, S), dy.to(_DT[0]).permute(0, 3, 1, 2), stride=stride,
                                          groups=K // cg)
         out.copy_(dw.permute(0, 2, 3, 1))
+
+    # ResNet-D pooled projection: the HIP contract (csrc/kernels/pool_proj.hip), the stash included
+    def pool_proj_fwd(self, x, w, sc, ap, in_bn=None):
+        a = _pre(x, in_bn, True)
+        if in_bn is not None:
+            a = a.to(x.dtype).to(_DT[0])   # (each term rounds where the activations are bf16)
+        ap.copy_(F.avg_pool2d(a.permute(0, 3, 1, 2), 2).permute(0, 2, 3, 1))
+        sc.copy_(ap.to(_DT[0]) @ w.to(_DT[0]).reshape(w.shape[0], -1).t())
+
+    def pool_proj_dgrad(self, d_out, w, da):
+        g = 0.25 * (d_out.to(_DT[0]) @ w.to(_DT[0]).reshape(w.shape[0], -1).t())
+        da.copy_(g.repeat_interleave(2, dim=1).repeat_interleave(2, dim=2))
 
     # Squeeze-and-Excitation: the HIP contract (ops named as csrc/kernels/se.hip's kernels), one split
     def se_splits(self, N, HW, C):

@@ -122,6 +122,7 @@ class BlockPlan:
     out: torch.Tensor               # block output
     grad_lo: int                    # lowest flat grad offset written by this block
     se: Optional[SEState] = None    # the gate on the residual branch (SE blocks only)
+    ap: Optional[torch.Tensor] = None   # ResNet-D: the pooled activation the projection's weight gradient reads
 
 
 class Executor:
@@ -153,6 +154,13 @@ class Executor:
                         backend.se_check(batch, blk.out_hw * blk.out_hw, blk.se.c, blk.se.hidden)
                     except ValueError as e:
                         raise ValueError(f"{spec.name}: {blk.se.name} cannot run on the HIP backend: {e}") from None
+                if blk.avg_down:
+                    try:
+                        backend.pool_proj_check((batch, blk.in_hw, blk.in_hw, blk.in_c),
+                                                (batch, blk.out_hw, blk.out_hw, blk.out_c))
+                    except ValueError as e:
+                        raise ValueError(f"{spec.name}: the pooled projection {blk.proj.name} cannot run on the HIP "
+                                         f"backend: {e}") from None
         # clip_grad_norm = c > 0: the gradient the optimizer reads is scaled by c / max(norm, c), norm
         # its global L2 norm (grad_scale included; TF's clip_by_global_norm). skip_nonfinite_grads: a
         # step whose norm is NaN / Inf changes no weight, momentum, bf16 copy, EMA or trust ratio.
@@ -531,6 +539,8 @@ class Executor:
             grad_lo = min([o.grad_lo for o in convs] + ([proj.grad_lo] if proj else []) +
                           [self.P.by_name[f"{b.bn.name}/gamma"].offset for b in bns])
             bp = BlockPlan(blk, x, bns, convs, proj, h_list, sc, out, grad_lo)
+            if blk.avg_down:
+                bp.ap = self._act(N, ohw, ohw, blk.in_c)
             if blk.se is not None:
                 e, P = blk.se, self.P
                 red, exp = f"{e.name}/reduce", f"{e.name}/expand"
@@ -831,11 +841,17 @@ class Executor:
         be = self.be
         bn = bp.bn
         self._bn_fwd(bn[0], train)
-        if bp.proj is not None:
+        if bp.proj is not None and not bp.blk.avg_down:
             xin, pro, fin = self._cin(bn[0])
             be.conv_fwd(xin, bp.proj.w, bp.sc, bp.proj.geom, in_bn=pro, in_fin=fin)
         for i, op in enumerate(bp.convs):
             last = i == len(bp.convs) - 1
+            if i == 1 and bp.blk.avg_down:
+                # ResNet-D: the pooled projection reads PUBLISHED scale / shift, so it follows the block's
+                # first conv, whose prologue finalizes and publishes them where no launch of its own does
+                xin, pro, fin = self._cin(bn[0])
+                assert fin is None, "the block's first conv publishes its BatchNorm"
+                be.pool_proj_fwd(xin, bp.proj.w, bp.sc, bp.ap, in_bn=pro)
             xin, pro, fin = self._cin(bn[i])
             if last and bp.se is not None:
                 # SE: the conv stores the branch u alone; squeeze -> gate -> excite, whose epilogue adds
@@ -1135,7 +1151,9 @@ class Executor:
             tgt = bufs[tgt_k]
             a_in, pro = (b.act, None) if b.act is not None else (b.src, b.ss)
             self._wgrad(a_in, dy, op.dw, op.geom, in_bn=pro, dy_buf=dy_buf, grouped=op.conv.groups > 1)
-            if i == 0 and bp.proj is not None:
+            if i == 0 and bp.ap is not None:   # ResNet-D: a plain 1x1 stride-1 weight gradient on the pooled stash
+                self._wgrad(bp.ap, d_out, bp.proj.dw, bp.proj.geom, dy_buf=bufs[cur])
+            elif i == 0 and bp.proj is not None:
                 self._wgrad(a_in, d_out, bp.proj.dw, bp.proj.geom, in_bn=pro, dy_buf=bufs[cur])
             self._claim(tgt)
             da = self._view(tgt, xin)        # d relu(bn(xin))
@@ -1146,7 +1164,10 @@ class Executor:
                 # the projection's data gradient first, the main conv's accumulating one last so
                 # that its (full-cover, stride-1) epilogue can carry the fused BN reduction
                 pj = bp.proj
-                self._dgrad(pj, d_out, da, accumulate=False)
+                if bp.ap is not None:        # ResNet-D: all four phases of da in one launch
+                    be.pool_proj_dgrad(d_out, pj.dg[0].wt, da)
+                else:
+                    self._dgrad(pj, d_out, da, accumulate=False)
                 self._dgrad(op, dy, da, accumulate=True, bn=b if fuse else None, bn_x=xin)
             else:
                 self._dgrad(op, dy, da, accumulate=False, bn=b if fuse else None, bn_x=xin)

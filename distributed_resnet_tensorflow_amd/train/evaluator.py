@@ -64,6 +64,16 @@ def checkpoint_se_ratio(FLAGS, prefix: str) -> int:
     return was
 
 
+def checkpoint_avg_down(FLAGS, prefix: str) -> bool:
+    """Whether the checkpoint was trained with ResNet-D shortcuts (its .meta; absent = False), so that
+    evaluation builds the network that was trained. An explicit --avg_down that contradicts it is an error."""
+    was = Saver.restore_meta(prefix)["avg_down"]
+    if "avg_down" in FLAGS and FLAGS.is_present("avg_down") and bool(FLAGS.avg_down) != was:
+        raise FlagsError(f"--avg_down={FLAGS.avg_down} contradicts checkpoint {prefix}, whose .meta records "
+                         f"avg_down={was} (drop the flag; the evaluator reads it from the .meta)")
+    return was
+
+
 def evaluate(FLAGS, eval_batch_size: int = 100, max_evals: int = -1):
     setup_logging(0)
     apply_thread_flags(FLAGS)
@@ -75,6 +85,8 @@ def evaluate(FLAGS, eval_batch_size: int = 100, max_evals: int = -1):
     first = latest_checkpoint(FLAGS.log_root)
     if first is not None and "se_ratio" in FLAGS:
         FLAGS.se_ratio = checkpoint_se_ratio(FLAGS, first)
+    if first is not None and "avg_down" in FLAGS:
+        FLAGS.avg_down = checkpoint_avg_down(FLAGS, first)
     spec = model_spec_from_flags(FLAGS)
     be = make_backend(cluster.device, getattr(FLAGS, "precision", "bf16"))
     top_k = int(getattr(FLAGS, "top_k", 0))

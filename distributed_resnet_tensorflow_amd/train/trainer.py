@@ -46,7 +46,8 @@ def model_spec_from_flags(FLAGS):
     # ResNet-v2 (resnet_model.py:74, resnet_imagenet_main.py:266-272: 25,551,401 params at size 50)
     width = FLAGS.width_multiplier if model == "wide_resnet" else 1
     return build_spec(ds, FLAGS.resnet_size, model=model, width=width, cardinality=FLAGS.cardinality,
-                      width_per_group=FLAGS.width_per_group, se_ratio=getattr(FLAGS, "se_ratio", 0))
+                      width_per_group=FLAGS.width_per_group, se_ratio=getattr(FLAGS, "se_ratio", 0),
+                      avg_down=bool(getattr(FLAGS, "avg_down", False)))
 
 
 def _meta(FLAGS, spec):
@@ -59,6 +60,8 @@ def _meta(FLAGS, spec):
                if FLAGS.model == "resnext" else {}),
             # Squeeze-and-Excitation only (absent = 0, no gate)
             **({"se_ratio": FLAGS.se_ratio} if getattr(FLAGS, "se_ratio", 0) else {}),
+            # ResNet-D shortcuts only (absent = False)
+            **({"avg_down": True} if getattr(FLAGS, "avg_down", False) else {}),
             "optimizer": FLAGS.optimizer, "eta": FLAGS.lars_eta, "eps": FLAGS.lars_eps,
             "adam_beta1": FLAGS.adam_beta1, "adam_beta2": FLAGS.adam_beta2, "adam_eps": FLAGS.adam_epsilon,
             "label_smoothing": FLAGS.label_smoothing, "ema_decay": FLAGS.ema_decay,
