@@ -193,4 +193,5 @@ class Saver:
         meta["adam_eps"] = float(meta.get("adam_eps", 1e-6))
         meta["se_ratio"] = int(meta.get("se_ratio", 0))   # absent = no Squeeze-and-Excitation gate
         meta["avg_down"] = bool(meta.get("avg_down", False))   # absent = strided projection shortcuts
+        meta["drop_path_rate"] = float(meta.get("drop_path_rate", 0.0))   # absent = no stochastic depth
         return meta

@@ -223,6 +223,13 @@ def validate(fv: "FlagValues") -> None:
         raise FlagsError("--se_ratio is not supported by --model=lrnet")
     if fv.avg_down and fv.model == "lrnet":
         raise FlagsError("--avg_down is not supported by --model=lrnet")
+    if not 0.0 <= fv.drop_path_rate < 1.0:
+        raise FlagsError(f"--drop_path_rate must be in [0, 1), got {fv.drop_path_rate!r}")
+    if fv.drop_path_rate > 0 and fv.model == "lrnet":
+        raise FlagsError("--drop_path_rate is not supported by --model=lrnet")
+    if fv.drop_path_rate > 0 and fv.se_ratio:
+        raise FlagsError("--drop_path_rate cannot be combined with --se_ratio: the Squeeze-and-Excitation kernels "
+                         "take no per-sample factor (the gate would have to carry it)")
 
 
 FLAGS = FlagValues()
@@ -298,6 +305,9 @@ def define_reference_flags(flag_values: FlagValues = FLAGS, **defaults) -> FlagV
       "0 = off. Any --model but lrnet.", fv)
     B("avg_down", False, "ResNet-D shortcuts: every stride-2 projection becomes a 2x2 / 2 average pool + a 1x1 "
       "stride-1 conv (same variables). Any --model but lrnet.", fv)
+    Fl("drop_path_rate", 0.0, "Stochastic depth: training drops block b of B's residual branch per sample with "
+       "probability rate * b / (B - 1) and scales the kept ones by 1 / (1 - p); 0 = off. Any --model but lrnet; "
+       "not with --se_ratio. Evaluation never drops.", fv)
     S("precision", "bf16", "Compute precision of the GPU path (bf16 activations, fp32 master).", fv)
     B("synthetic_data", False, "Use synthetic data of the dataset's shape (benchmarks).", fv)
     I("save_checkpoint_secs", 60, "Checkpoint period in seconds (reference: 60).", fv)

@@ -46,14 +46,16 @@ def _maxpool_same(x, k=3, s=2):
 
 
 def forward(spec: NetSpec, p: Dict[str, torch.Tensor], state: Dict[str, tuple], images_nhwc: torch.Tensor,
-            training: bool = True) -> torch.Tensor:
+            training: bool = True, drop_path=None) -> torch.Tensor:
     """Logits of the network. `p` maps TF variable names to tensors in TF layout; `state`
-    maps BN names to (moving_mean, moving_variance) tensors updated in place when training."""
+    maps BN names to (moving_mean, moving_variance) tensors updated in place when training.
+    drop_path: stochastic depth's factor table [blocks][N] (keep / (1 - p) per block and sample) scaling
+    each residual branch of a training forward; evaluation never drops."""
     x = images_nhwc[..., :spec.in_channels].to(p[f"{spec.stem.name}/kernel"].dtype).permute(0, 3, 1, 2)
     x = _conv(x, p[f"{spec.stem.name}/kernel"], spec.stem)
     if spec.maxpool:
         x = _maxpool_same(x)
-    for blk in spec.blocks:
+    for bi, blk in enumerate(spec.blocks):
         shortcut = x
         a = _bn_relu(x, blk.bn1, p, state, training)
         if blk.proj is not None:   # (ResNet-D: on the 2x2 / 2 average-pooled activation)
@@ -66,14 +68,16 @@ def forward(spec: NetSpec, p: Dict[str, torch.Tensor], state: Dict[str, tuple], 
             z = h.mean(dim=(2, 3))
             hid = torch.relu(z @ p[f"{e}/reduce/kernel"] + p[f"{e}/reduce/bias"])
             h = h * torch.sigmoid(hid @ p[f"{e}/expand/kernel"] + p[f"{e}/expand/bias"])[:, :, None, None]
+        if drop_path is not None and training:
+            h = h * drop_path[bi].to(h.dtype)[:, None, None, None]
         x = h + shortcut
     x = _bn_relu(x, spec.final_bn, p, state, training)
     x = x.mean(dim=(2, 3))
     return x @ p[f"{spec.dense_name}/kernel"] + p[f"{spec.dense_name}/bias"]
 
 
-def loss_fn(spec, p, state, images, labels, weight_decay=0.0, training=True, label_smoothing=0.0):
-    logits = forward(spec, p, state, images, training)
+def loss_fn(spec, p, state, images, labels, weight_decay=0.0, training=True, label_smoothing=0.0, drop_path=None):
+    logits = forward(spec, p, state, images, training, drop_path=drop_path)
     xent = F.cross_entropy(logits, labels.long(), label_smoothing=label_smoothing)
     cost = xent
     if weight_decay:

@@ -90,6 +90,7 @@ class Block:
     bns: List[BN]             # BNs preceding convs[1:], i.e. bn2 (and bn3)
     se: Optional[SE] = None   # gate on the residual branch (se_ratio > 0)
     avg_down: bool = False    # ResNet-D shortcut: proj is 1x1 stride 1 on the 2x2 / 2 average-pooled input
+    drop_rate: float = 0.0    # stochastic depth: probability that a training step drops the residual branch
 
 
 @dataclass
@@ -216,6 +217,20 @@ def _check_se_ratio(se_ratio: int):
         raise ValueError(f"se_ratio must be one of {SE_RATIOS}, got {se_ratio!r}")
 
 
+def drop_rates(rate: float, blocks: int) -> List[float]:
+    """Stochastic depth's linear rule (Huang et al. 2016): block b of B, in network order, drops its residual
+    branch with probability rate * b / (B - 1): 0 for the first block, `rate` for the last."""
+    if not 0.0 <= rate < 1.0:
+        raise ValueError(f"drop_path_rate must be in [0, 1), got {rate!r}")
+    return [rate * b / (blocks - 1) if blocks > 1 else 0.0 for b in range(blocks)]
+
+
+def _set_drop_rates(spec: NetSpec, rate: float) -> NetSpec:
+    for blk, p in zip(spec.blocks, drop_rates(float(rate), len(spec.blocks))):
+        blk.drop_rate = p
+    return spec
+
+
 def _stage(spec: NetSpec, nm: _Namer, kind: str, stage: int, filters: int, blocks: int, stride: int,
            in_c: int, hw: int, width: int = 1, groups: int = 1, width_per_group: int = 64,
            se_ratio: int = 0, avg_down: bool = False) -> tuple[int, int]:
@@ -251,9 +266,10 @@ def _stage(spec: NetSpec, nm: _Namer, kind: str, stage: int, filters: int, block
 
 
 def cifar_resnet_v2(resnet_size: int = 50, num_classes: int = 10, se_ratio: int = 0,
-                    avg_down: bool = False) -> NetSpec:
+                    avg_down: bool = False, drop_path_rate: float = 0.0) -> NetSpec:
     """cifar10_resnet_v2_generator (reference resnet_model_official.py:217-278); se_ratio > 0 ->
-    every block gated by Squeeze-and-Excitation (extension); avg_down -> ResNet-D shortcuts (extension)."""
+    every block gated by Squeeze-and-Excitation (extension); avg_down -> ResNet-D shortcuts (extension);
+    drop_path_rate > 0 -> stochastic depth, Block.drop_rate by the linear rule (extension)."""
     if resnet_size % 6 != 2:
         raise ValueError(f"resnet_size must be 6n + 2: {resnet_size}")
     _check_se_ratio(se_ratio)
@@ -267,7 +283,7 @@ def cifar_resnet_v2(resnet_size: int = 50, num_classes: int = 10, se_ratio: int 
         c, hw = _stage(spec, nm, "basic", stage, f, n, s, c, hw, se_ratio=se_ratio, avg_down=avg_down)
     spec.final_bn = BN(nm.next_bn(), c)
     spec.final_hw, spec.final_c = hw, c
-    return spec
+    return _set_drop_rates(spec, drop_path_rate)
 
 
 IMAGENET_SIZES = {
@@ -282,13 +298,14 @@ IMAGENET_SIZES = {
 
 def imagenet_resnet_v2(resnet_size: int = 50, num_classes: int = 1001, width: int = 1,
                        image_size: int = 224, groups: int = 1, width_per_group: int = 64,
-                       se_ratio: int = 0, avg_down: bool = False) -> NetSpec:
+                       se_ratio: int = 0, avg_down: bool = False, drop_path_rate: float = 0.0) -> NetSpec:
     """imagenet_resnet_v2 (reference resnet_model_official.py:281-366); width=2 -> WRN-50-2 (extension);
     groups > 1 -> ResNeXt (extension): the bottleneck's 3x3 conv is grouped, its width in stage s is
     groups * width_per_group * 2^(s-1) (32x4d: 128 / 256 / 512 / 1024), the block output stays filters * 4.
     se_ratio > 0 -> every block gated by Squeeze-and-Excitation, hidden width max(C / se_ratio, 8) (extension).
     avg_down -> ResNet-D shortcuts (extension): every stride-2 projection becomes a 2x2 / 2 average pool + a 1x1
-    stride-1 conv (Block.avg_down); variable names and shapes are unchanged."""
+    stride-1 conv (Block.avg_down); variable names and shapes are unchanged.
+    drop_path_rate > 0 -> stochastic depth (extension): Block.drop_rate by the linear rule; variables unchanged."""
     if resnet_size not in IMAGENET_SIZES:
         raise ValueError(f"Not a valid resnet_size: {resnet_size}")
     kind, layers = IMAGENET_SIZES[resnet_size]
@@ -315,12 +332,12 @@ def imagenet_resnet_v2(resnet_size: int = 50, num_classes: int = 1001, width: in
                        width_per_group=width_per_group, se_ratio=se_ratio, avg_down=avg_down)
     spec.final_bn = BN(nm.next_bn(), c)
     spec.final_hw, spec.final_c = hw, c
-    return spec
+    return _set_drop_rates(spec, drop_path_rate)
 
 
 def build_spec(dataset: str, resnet_size: int | None = None, model: str = "resnet", width: int = 1,
                num_classes: int | None = None, cardinality: int = 32, width_per_group: int = 4,
-               se_ratio: int = 0, avg_down: bool = False) -> NetSpec:
+               se_ratio: int = 0, avg_down: bool = False, drop_path_rate: float = 0.0) -> NetSpec:
     """Network selection of the reference ResNet wrapper (resnet_model.py:71-74, size fixed to 50
     there; `--resnet_size` makes it selectable here). cifar100 is supported."""
     if model == "wide_resnet":
@@ -329,11 +346,13 @@ def build_spec(dataset: str, resnet_size: int | None = None, model: str = "resne
         if dataset != "imagenet":
             raise ValueError("model=resnext is an ImageNet network (bottleneck blocks)")
         return imagenet_resnet_v2(resnet_size or 50, num_classes or 1001, groups=cardinality,
-                                  width_per_group=width_per_group, se_ratio=se_ratio, avg_down=avg_down)
+                                  width_per_group=width_per_group, se_ratio=se_ratio, avg_down=avg_down,
+                                  drop_path_rate=drop_path_rate)
     if dataset in ("cifar10", "cifar100", "cifar"):
         nc = num_classes or (100 if dataset == "cifar100" else 10)
-        return cifar_resnet_v2(resnet_size or 50, nc, se_ratio=se_ratio, avg_down=avg_down)
+        return cifar_resnet_v2(resnet_size or 50, nc, se_ratio=se_ratio, avg_down=avg_down,
+                               drop_path_rate=drop_path_rate)
     if dataset == "imagenet":
         return imagenet_resnet_v2(resnet_size or 50, num_classes or 1001, width=width, se_ratio=se_ratio,
-                                  avg_down=avg_down)
+                                  avg_down=avg_down, drop_path_rate=drop_path_rate)
     raise ValueError(f"unknown dataset {dataset}")

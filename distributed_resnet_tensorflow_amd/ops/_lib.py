@@ -109,6 +109,13 @@ class DrnPoolProjArgs(ctypes.Structure):
                [(n, c_int) for n in ("N", "H", "W", "Cin", "Cout", "P", "Q", "M", "K", "NC", "ncb")]
 
 
+class DrnDropPathArgs(ctypes.Structure):
+    """Mirror of csrc/kernels/drop_path.hip `struct DrnDropPathArgs` (stochastic depth; the entry points fill
+    every field after stats_rep)."""
+    _fields_ = [(n, c_p) for n in ("x", "y", "out", "f", "stats")] + \
+               [(n, c_int) for n in ("N", "HW", "C", "stats_rep", "S", "pps", "slab", "cpw", "planes", "pad_")]
+
+
 class DrnConvCfgInfo(ctypes.Structure):
     """Mirror of csrc/include/drn_conv.h `struct DrnConvCfgInfo` (drn_conv_cfg_info)."""
     _fields_ = [(n, c_int) for n in ("kind", "bp", "bc", "waves_p", "ns", "nw", "bk", "nh", "il", "ks")]
@@ -149,6 +156,11 @@ _SIGS = {
     "drn_pool_proj_fwd": ([ctypes.POINTER(DrnPoolProjArgs), c_p], c_int),
     "drn_pool_proj_dgrad": ([ctypes.POINTER(DrnPoolProjArgs), c_p], c_int),
     "drn_pool_proj_args_size": ([], c_int),
+    # stochastic depth (drop_path.hip): scaled residual add (+ statistics), branch gradient
+    "drn_drop_path_fwd": ([ctypes.POINTER(DrnDropPathArgs), c_p], c_int),
+    "drn_drop_path_bwd": ([ctypes.POINTER(DrnDropPathArgs), c_p], c_int),
+    "drn_drop_path_splits": ([c_int, c_int, c_int], c_int),
+    "drn_drop_path_args_size": ([], c_int),
     "drn_splitk_reduce": ([c_p, c_p, c_i64, c_int, c_f, c_int, c_p], c_int),
     "drn_bn_stats": ([c_p, c_p, c_int, c_int, c_int, c_int, c_p], c_int),
     "drn_bn_finalize": ([c_p, c_int, c_int, c_f, c_p, c_p, c_f, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_p], c_int),
@@ -286,7 +298,8 @@ def lib():
             fn.restype = res
         for name, st in (("drn_bn_fin_size", DrnBnFin), ("drn_conv_args_size", DrnConvFwdArgs),
                          ("drn_wgrad_args_size", DrnConvWgradArgs), ("drn_gconv_args_size", DrnGconvArgs),
-                         ("drn_se_args_size", DrnSeArgs), ("drn_pool_proj_args_size", DrnPoolProjArgs)):
+                         ("drn_se_args_size", DrnSeArgs), ("drn_pool_proj_args_size", DrnPoolProjArgs),
+                         ("drn_drop_path_args_size", DrnDropPathArgs)):
             if getattr(h, name)() != ctypes.sizeof(st):
                 raise KernelLibraryError(f"{st.__name__} layout mismatch between Python and {LIB_PATH.name}")
         _check_stamp(h)

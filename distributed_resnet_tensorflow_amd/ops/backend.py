@@ -17,6 +17,7 @@ Op contract (NHWC activations, KRSC conv weights, fp32 statistics):
   box_preprocess(packed, desc, out, mean, std, jitter)       Inception-style input: box resample, colour jitter
   grad_guard(g, grad_scale, clip, guard, skip_in, ws, rec)   global-norm clip + non-finite step guard
   se_squeeze / se_gate_fwd / se_excite / se_gate_bwd / se_gate_wgrad / se_scale_bwd   Squeeze-and-Excitation gate
+  drop_path_fwd(u, shortcut, f, out, stats) / drop_path_bwd(d_out, f, du)   stochastic depth, f per sample
 where pre(x) = relu(x * scale + shift) when in_bn = (scale, shift) is given.
 """
 from __future__ import annotations
@@ -902,6 +903,51 @@ class HipBackend(_Common):
         a = self._pool_proj_args(da.shape, d_out.shape, dy=d_out, w=w, da=da)
         _lib.check(self.L.drn_pool_proj_dgrad(ctypes.byref(a), self.stream()), "drn_pool_proj_dgrad")
 
+    # -- stochastic depth (csrc/kernels/drop_path.hip) ----------------------------------------------
+    @staticmethod
+    def drop_path_check(N: int, HW: int, C: int):
+        """Raises unless an [N, HW, C] residual add is inside the drop-path kernels' domain (needs no device)."""
+        if not (1 <= N <= 65535 and HW >= 1 and C >= 8 and C % 8 == 0):
+            raise ValueError(f"drop path outside the HIP kernels' domain (C % 8 == 0, N <= 65535): N {N}, HW {HW}, "
+                             f"C {C}")
+
+    def drop_path_splits(self, N: int, HW: int, C: int) -> int:
+        """Pixel splits per sample (workgroups along a sample's pixels) the kernels use for this geometry."""
+        self.drop_path_check(N, HW, C)
+        return int(self.L.drn_drop_path_splits(N, HW, C))
+
+    def _drop_path_args(self, f, **tensors):
+        """Argument block; x / y / out bf16 [N, ..., C], contiguous and 16-byte aligned; f fp32 [N]."""
+        t0 = tensors["x"]
+        N, C = t0.shape[0], t0.shape[-1]
+        self.drop_path_check(N, t0.numel() // (N * C), C)
+        a = _lib.DrnDropPathArgs()
+        a.N, a.HW, a.C = N, t0.numel() // (N * C), C
+        if not (f.shape == (N,) and f.is_contiguous() and f.dtype == torch.float32):
+            raise ValueError(f"drop path: the factors must be a contiguous fp32 [{N}] row")
+        a.f = f.data_ptr()
+        for k, t in tensors.items():
+            if not (t.shape == t0.shape and t.is_contiguous() and t.dtype == torch.bfloat16 and t.data_ptr() % 16 == 0):
+                raise ValueError(f"drop path: {k} must be contiguous bf16 of shape {tuple(t0.shape)}, 16-byte aligned")
+            setattr(a, k, t.data_ptr())
+        return a
+
+    def drop_path_fwd(self, u, shortcut, f, out, stats=None):
+        """out[n] = bf16(shortcut[n] + f[n] * u[n]) (one rounding); stats[R, 2, C] += sum, sum of squares of the
+        stored out. A sample with f[n] == 0 never reads u: out gets the shortcut's bits (nothing is stored when
+        out is the shortcut tensor itself)."""
+        a = self._drop_path_args(f, x=u, y=shortcut, out=out)
+        if stats is not None:
+            if not (stats.dtype == torch.float32 and stats.is_contiguous() and stats.numel() % (2 * a.C) == 0):
+                raise ValueError("drop path: the statistics accumulator must be fp32 [rep][2][C]")
+            a.stats, a.stats_rep = stats.data_ptr(), stats.numel() // (2 * a.C)
+        _lib.check(self.L.drn_drop_path_fwd(ctypes.byref(a), self.stream()), "drn_drop_path_fwd")
+
+    def drop_path_bwd(self, d_out, f, du):
+        """du[n] = bf16(f[n] * d_out[n]); a sample with f[n] == 0 gets zeros and d_out[n] is never read."""
+        a = self._drop_path_args(f, x=d_out, out=du)
+        _lib.check(self.L.drn_drop_path_bwd(ctypes.byref(a), self.stream()), "drn_drop_path_bwd")
+
     # -- Squeeze-and-Excitation (csrc/kernels/se.hip) ---------------------------------------------
     @staticmethod
     def se_check(N: int, HW: int, C: int, Cr: int):
@@ -1591,6 +1637,21 @@ class RefBackend(_Common):
     def pool_proj_dgrad(self, d_out, w, da):
         g = 0.25 * (d_out.to(_DT[0]) @ w.to(_DT[0]).reshape(w.shape[0], -1).t())
         da.copy_(g.repeat_interleave(2, dim=1).repeat_interleave(2, dim=2))
+
+    # stochastic depth: the HIP contract (csrc/kernels/drop_path.hip); a dropped sample's u / d_out is not read
+    def drop_path_fwd(self, u, shortcut, f, out, stats=None):
+        C = u.shape[-1]
+        fv = f.to(_DT[0])[:, None, None, None]
+        branch = torch.where(fv != 0, fv * u.to(_DT[0]), torch.zeros((), dtype=_DT[0]))
+        out.copy_(shortcut.to(_DT[0]) + branch)   # (rounds where out is bf16)
+        if stats is not None:
+            yy = out.to(_DT[0]).reshape(-1, C)
+            stats.view(-1)[:C].add_(yy.sum(0))
+            stats.view(-1)[C:2 * C].add_((yy * yy).sum(0))
+
+    def drop_path_bwd(self, d_out, f, du):
+        fv = f.to(_DT[0])[:, None, None, None]
+        du.copy_(torch.where(fv != 0, fv * d_out.to(_DT[0]), torch.zeros((), dtype=_DT[0])))
 
     # Squeeze-and-Excitation: the HIP contract (ops named as csrc/kernels/se.hip's kernels), one split
     def se_splits(self, N, HW, C):

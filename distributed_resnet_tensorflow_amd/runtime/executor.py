@@ -30,7 +30,7 @@ from typing import Callable, List, Optional
 
 import torch
 
-from ..models.spec import Block, BN, Conv, NetSpec
+from ..models.spec import Block, BN, Conv, NetSpec, drop_rates
 from ..ops.backend import BnCfin, ConvGeom, OutMap, dgrad_geom, tflip_desc, tflip_table
 from .params import ParamStore
 
@@ -123,6 +123,7 @@ class BlockPlan:
     grad_lo: int                    # lowest flat grad offset written by this block
     se: Optional[SEState] = None    # the gate on the residual branch (SE blocks only)
     ap: Optional[torch.Tensor] = None   # ResNet-D: the pooled activation the projection's weight gradient reads
+    drop: Optional[torch.Tensor] = None  # stochastic depth (drop_rate > 0): the block's row [N] of drop_table
 
 
 class Executor:
@@ -133,8 +134,28 @@ class Executor:
                  lars_eps: float = 1e-9, label_smoothing: float = 0.0, top_k: int = 0, ema_decay: float = 0.0,
                  ema_warmup: bool = True, mix: bool = False, clip_grad_norm: float = 0.0,
                  skip_nonfinite_grads: bool = False, adam_beta1: float = 0.9, adam_beta2: float = 0.999,
-                 adam_eps: float = 1e-6):
+                 adam_eps: float = 1e-6, drop_path_rate: Optional[float] = None):
         self.spec, self.N, self.be = spec, batch, backend
+        # stochastic depth: a training step computes out[n] = shortcut[n] + f[b][n] * u[n] in every block b
+        # whose drop probability is > 0 (spec Block.drop_rate, or the linear rule over drop_path_rate when
+        # given), f = keep / (1 - p) read from drop_table [blocks][N] in device memory like the LR
+        # (set_drop_path; all ones until set), so graph and plan replays follow each step's draws. Such a
+        # block's last conv writes the raw branch u; csrc/kernels/drop_path.hip adds the shortcut and
+        # produces the next BatchNorm's statistics, and scales the gradient that enters the last conv's
+        # data and weight gradients. Evaluation never drops (the scaling is inverted). All probabilities 0:
+        # nothing is allocated and the step makes exactly the calls it made before
+        self.drop_rates = [float(blk.drop_rate) for blk in spec.blocks] if drop_path_rate is None \
+            else drop_rates(float(drop_path_rate), len(spec.blocks))
+        for blk, p in zip(spec.blocks, self.drop_rates):
+            if p > 0 and blk.se is not None:
+                raise ValueError(f"{spec.name}: stochastic depth on a Squeeze-and-Excitation block is not supported "
+                                 "(se_ratio and drop_path_rate exclude each other)")
+            if p > 0 and backend.name == "hip":
+                try:
+                    backend.drop_path_check(batch, blk.out_hw * blk.out_hw, blk.out_c)
+                except ValueError as e:
+                    raise ValueError(f"{spec.name}: stochastic depth on block {blk.stage}.{blk.index} cannot run on "
+                                     f"the HIP backend: {e}") from None
         if backend.name == "hip":
             # grouped convs outside the HIP kernels' domain (e.g. ResNeXt 32x8d's 64-wide groups in stage 4)
             # are refused here, before anything is allocated; the reference backend takes any
@@ -503,6 +524,12 @@ class Executor:
             self.stem_stats, self.stem_G = self._stats_for(N * hs * hs, sp.stem.cout)
             x, x_stats, x_G = self.stem_out, self.stem_stats, self.stem_G
         self.blocks: List[BlockPlan] = []
+        self.drop_table = self.drop_u = None
+        if any(p > 0 for p in self.drop_rates):
+            self.drop_table = torch.ones(len(sp.blocks), N, dtype=self.fdt, device=self.device)
+            # the raw branch u of the block being computed: dead once the add has run, so one buffer serves all
+            self.drop_u = self._act(max(N * blk.out_hw * blk.out_hw * blk.out_c
+                                        for blk, p in zip(sp.blocks, self.drop_rates) if p > 0))
         ws_need = be.wgrad_ws_elems(N * hs * hs, sp.stem.cout, sp.stem.k, sp.stem.k, sp.stem.cin_store)
         if self.stem_pack:  # the packed stem's gradient has fewer k-tiles, so it may take more splits
             ws_need = max(ws_need, be.wgrad_ws_elems(N * hs * hs, *self.stem_dw4.shape))
@@ -541,6 +568,8 @@ class Executor:
             bp = BlockPlan(blk, x, bns, convs, proj, h_list, sc, out, grad_lo)
             if blk.avg_down:
                 bp.ap = self._act(N, ohw, ohw, blk.in_c)
+            if self.drop_rates[len(self.blocks)] > 0:
+                bp.drop = self.drop_table[len(self.blocks)]
             if blk.se is not None:
                 e, P = blk.se, self.P
                 red, exp = f"{e.name}/reduce", f"{e.name}/expand"
@@ -627,6 +656,8 @@ class Executor:
             nbuf = 6 if self.side is not None else 3
         if any(bp.se is not None for bp in self.blocks):
             nbuf += 1   # an SE block's backward holds d(out) AND the gated branch's gradient du
+        if self.drop_table is not None:
+            nbuf += 1   # likewise d(out) and the scaled branch gradient of a stochastic-depth block
         self.g_bufs = [self._act(max_act) for _ in range(nbuf)]
         self.g_a, self.g_b, self.g_c = self.g_bufs[:3]
         self._lru: List[int] = []
@@ -825,6 +856,17 @@ class Executor:
             raise ValueError(f"the mix table has {t.shape[0]} records, the batch {self.N} samples")
         self.mix_table.copy_(t, non_blocking=True)
 
+    def set_drop_path(self, table):
+        """The stochastic-depth factors of the coming training step: [blocks, N], f[b][n] = 0 (sample n drops
+        block b's branch) or 1 / (1 - p_b) (data/drop_path.py draws them); rows of blocks whose probability is
+        0 are not read. Copied into drop_table, the device buffer the recorded kernels read, in stream order."""
+        if self.drop_table is None:
+            raise RuntimeError("this executor has no stochastic depth (every block's drop rate is 0)")
+        t = torch.as_tensor(table)
+        if tuple(t.shape) != tuple(self.drop_table.shape):
+            raise ValueError(f"the drop-path table is {tuple(t.shape)}, this executor's {tuple(self.drop_table.shape)}")
+        self.drop_table.copy_(t, non_blocking=True)
+
     def _check(self, t: torch.Tensor, what: str):
         """DRN_CHECK_NAN=1 debug mode: synchronous finiteness check naming the failing stage."""
         if not bool(torch.isfinite(t.float()).all()):
@@ -862,6 +904,12 @@ class Executor:
                 be.se_gate_fwd(e.cells, e.hw, e.w1, e.b1, e.w2, e.b2, e.z, e.h, e.s)
                 be.se_excite(e.u, bp.sc if bp.proj is not None else bp.x, e.s, bp.out,
                              stats=bp.out_stats if train else None)
+            elif last and bp.drop is not None and train:
+                # stochastic depth: the conv stores the branch u alone; the add scales it per sample, adds the
+                # shortcut and produces the next BatchNorm's statistics in the conv epilogue's place
+                u = self._view(self.drop_u, bp.out)
+                be.conv_fwd(xin, op.w, u, op.geom, in_bn=pro, in_fin=fin)
+                be.drop_path_fwd(u, bp.sc if bp.proj is not None else bp.x, bp.drop, bp.out, stats=bp.out_stats)
             elif last:
                 res = bp.sc if bp.proj is not None else bp.x
                 be.conv_fwd(xin, op.w, bp.out, op.geom, in_bn=pro, residual=res, in_fin=fin,
@@ -1145,6 +1193,14 @@ class Executor:
             be.se_gate_bwd(e.cells, e.hw, e.w1, e.w2, e.h, e.s, e.dl2, e.dh, e.dzs)
             be.se_scale_bwd(d_out, e.s, e.dzs, dy)
             self._on_side(lambda: be.se_gate_wgrad(e.z, e.h, e.dl2, e.dh, e.dw1, e.db1, e.dw2, e.db2))
+        if bp.drop is not None:
+            # stochastic depth: du = f * d_out is the last conv's dy; d_out itself stays live as the
+            # shortcut's gradient
+            dy_k = self._take(bufs, (cur,))
+            dy_buf = bufs[dy_k]
+            self._claim(dy_buf)
+            dy = self._view(dy_buf, bp.out)
+            be.drop_path_bwd(d_out, bp.drop, dy)
         for i in reversed(range(len(bp.convs))):
             op, xin, b = bp.convs[i], ins[i], bp.bn[i]
             tgt_k = self._take(bufs, (cur, dy_k))

@@ -87,6 +87,8 @@ def evaluate(FLAGS, eval_batch_size: int = 100, max_evals: int = -1):
         FLAGS.se_ratio = checkpoint_se_ratio(FLAGS, first)
     if first is not None and "avg_down" in FLAGS:
         FLAGS.avg_down = checkpoint_avg_down(FLAGS, first)
+    if "drop_path_rate" in FLAGS:
+        FLAGS.drop_path_rate = 0.0   # stochastic depth shapes training steps only: the evaluated network is unscaled
     spec = model_spec_from_flags(FLAGS)
     be = make_backend(cluster.device, getattr(FLAGS, "precision", "bf16"))
     top_k = int(getattr(FLAGS, "top_k", 0))

@@ -11,6 +11,9 @@ Mixup / CutMix (training feeders given a data.mix.MixSampler): the batch's mix t
 the batch and staged with its other copies; after the preprocess kernel the images are mixed in
 place with their reversal (csrc/kernels/mix.hip) and the table goes to the executor, whose loss
 kernel reads it. `state()` then carries `mix_batch`, the number of draws consumed.
+
+Stochastic depth (training feeders given a data.drop_path.DropPathSampler): the batch's factor table is
+drawn and staged the same way and handed to the executor with the batch; `state()` carries `drop_batch`.
 """
 from __future__ import annotations
 
@@ -29,13 +32,20 @@ def _mix_host_table(sampler, index: int, labels, pin: bool):
     return t.pin_memory() if pin else t
 
 
+def _drop_host_table(sampler, index: int, pin: bool):
+    """The fp32 [blocks, N] host tensor (page-locked when `pin`) of sampler.draw(index)."""
+    t = torch.from_numpy(sampler.draw(index))
+    return t.pin_memory() if pin else t
+
+
 class SyntheticFeeder:
     """mix (a data.mix.MixSampler): the static batch stays in a buffer of the feeder's own and every
     next() mixes it, with the draw of that batch, out of place into ex.images (mixing the static
     batch in place would compound from step to step)."""
 
-    def __init__(self, ex, seed: int = 0, mix=None, mix_index: int = 0):
+    def __init__(self, ex, seed: int = 0, mix=None, mix_index: int = 0, drop=None, drop_index: int = 0):
         self.ex, self.mix, self._mix_index = ex, mix, int(mix_index)
+        self.drop, self._drop_index = drop, int(drop_index)
         ex.be.synthetic_images(ex.images, seed)
         g = torch.Generator().manual_seed(seed)
         self.h_labels = torch.randint(0, ex.spec.num_classes, (ex.N,), generator=g, dtype=torch.int32)
@@ -52,13 +62,17 @@ class SyntheticFeeder:
             ex.be.mix_pairs(self.pristine, ex.images, self.d_table)
             ex.set_mix(self.d_table)
             self._mix_index += 1
+        if self.drop is not None:
+            self.ex.set_drop_path(_drop_host_table(self.drop, self._drop_index, self.ex.device.type == "cuda"))
+            self._drop_index += 1
         return True
 
     def prefetch(self):
         pass
 
     def state(self):
-        return {"mix_batch": self._mix_index} if self.mix is not None else {}
+        return {**({"mix_batch": self._mix_index} if self.mix is not None else {}),
+                **({"drop_batch": self._drop_index} if self.drop is not None else {})}
 
     def close(self):
         pass
@@ -104,7 +118,7 @@ class _StagedFeeder:
     COPY_STREAM = True
     COPY_STREAM_PRIORITY = -1
 
-    def _init_staging(self, ex, mix=None, mix_index: int = 0):
+    def _init_staging(self, ex, mix=None, mix_index: int = 0, drop=None, drop_index: int = 0):
         """mix (a data.mix.MixSampler, training feeders only): batch i of this feeder is mixed with
         the sampler's draw mix_index + i. The table is drawn and staged with the batch's other
         copies; _consume mixes ex.images in place after the preprocess kernel and hands the table to
@@ -112,6 +126,10 @@ class _StagedFeeder:
         self.ex = ex
         self.mix, self._mix_index = mix, int(mix_index)
         self.d_table = torch.empty(ex.N, 8, dtype=torch.int32, device=ex.device) if mix is not None else None
+        # drop (a data.drop_path.DropPathSampler, training feeders only): batch i gets the sampler's draw
+        # drop_index + i, staged with the batch's other copies and handed to the executor by _consume
+        self.drop, self._drop_index = drop, int(drop_index)
+        self.d_drop = torch.empty_like(ex.drop_table, dtype=torch.float32) if drop is not None else None
         self.gpu = ex.device.type == "cuda"
         prio = int(os.environ.get("DRN_COPY_STREAM_PRIORITY", str(self.COPY_STREAM_PRIORITY)))
         self.copy_stream = (torch.cuda.Stream(device=ex.device, priority=prio)
@@ -129,21 +147,29 @@ class _StagedFeeder:
         st = self.loader.state()
         if self.mix is not None:
             st["mix_batch"] = self._mix_index
+        if self.drop is not None:
+            st["drop_batch"] = self._drop_index
         return st
 
     def _mix_pairs(self, labels):
         """[(device table, host table)] of the batch being staged (empty without mixing)."""
+        pairs = []
+        if self.drop is not None:   # (staged wherever the mix table is: the stochastic-depth factors)
+            pairs.append((self.d_drop, _drop_host_table(self.drop, self._drop_index, self.gpu)))
+            self._drop_index += 1
         if self.mix is None:
-            return []
+            return pairs
         t = _mix_host_table(self.mix, self._mix_index, labels, self.gpu)
         self._mix_index += 1
-        return [(self.d_table, t)]
+        return pairs + [(self.d_table, t)]
 
     def _mix_consume(self):
         """After the preprocess kernel: mix ex.images in place, hand the table to the executor."""
         if self.mix is not None:
             self.ex.be.mix_pairs(self.ex.images, self.ex.images, self.d_table)
             self.ex.set_mix(self.d_table)
+        if self.drop is not None:
+            self.ex.set_drop_path(self.d_drop)
 
     def _stage(self, pairs):
         """pairs: [(device dst, host src)]; enqueues the copies on the copy stream (or, without
@@ -217,13 +243,15 @@ class _StagedFeeder:
 class CifarFeeder(_StagedFeeder):
     COPY_STREAM = False
 
-    def __init__(self, ex, loader: "cifar_data.CifarLoader", is_training: bool, mix=None, mix_index: int = 0):
+    def __init__(self, ex, loader: "cifar_data.CifarLoader", is_training: bool, mix=None, mix_index: int = 0,
+                 drop=None, drop_index: int = 0):
         self.loader, self.train = loader, is_training
         N, dev = ex.N, ex.device
         self.d_img = torch.empty(N, 32, 32, 3, dtype=torch.uint8, device=dev)
         self.d_par = torch.empty(N, 3, dtype=torch.int32, device=dev)
         self.d_lab = torch.empty(N, dtype=torch.int32, device=dev)
-        self._init_staging(ex, mix if is_training else None, mix_index)   # (evaluation never mixes)
+        # (evaluation never mixes and never drops)
+        self._init_staging(ex, mix if is_training else None, mix_index, drop if is_training else None, drop_index)
         self._prefetch()
 
     def _stage_item(self, item):
@@ -237,7 +265,8 @@ class CifarFeeder(_StagedFeeder):
 
 
 class ImagenetFeeder(_StagedFeeder):
-    def __init__(self, ex, loader, is_training: bool, max_bytes: int = 64 << 20, mix=None, mix_index: int = 0):
+    def __init__(self, ex, loader, is_training: bool, max_bytes: int = 64 << 20, mix=None, mix_index: int = 0,
+                 drop=None, drop_index: int = 0):
         from ..data import imagenet as inet
         self.inet = inet
         self.loader = loader
@@ -250,7 +279,8 @@ class ImagenetFeeder(_StagedFeeder):
         self.d_lab = torch.empty(ex.N, dtype=torch.int32, device=ex.device)
         self.h_packed = None  # CPU path: the reference backend preprocesses from host memory
         self.h_desc = None
-        self._init_staging(ex, mix if is_training else None, mix_index)   # (evaluation never mixes)
+        # (evaluation never mixes and never drops)
+        self._init_staging(ex, mix if is_training else None, mix_index, drop if is_training else None, drop_index)
         self._prefetch()
 
     def _stage_item(self, item):

@@ -110,6 +110,8 @@ class SummaryHook(Hook):
             scalars["ema/decay"] = m["ema_decay"]
         if "mix_lam" in m:    # (--mixup_alpha / --cutmix_alpha: the batch mean of the target weight lam)
             scalars["mix/lam"] = m["mix_lam"]
+        if "drop_path_kept" in m:   # (--drop_path_rate: the share of residual branches the last step kept)
+            scalars["drop_path/kept_fraction"] = m["drop_path_kept"]
         if "grad_global_norm" in m:  # (--clip_grad_norm / --skip_nonfinite_grads: the guard's device record)
             scalars.update({"grad/global_norm": m["grad_global_norm"], "grad/clip_scale": m["grad_clip_scale"],
                             "grad/clipped_steps": m["grad_clipped_steps"],

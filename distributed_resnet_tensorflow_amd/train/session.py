@@ -480,6 +480,10 @@ class TrainingSession:
             if self.ex.mix_table is not None:
                 # the batch mean of lam of the last step's mix table (column 1 holds lam's bits)
                 m["mix_lam"] = float(self.ex.mix_table[:, 1].contiguous().view(torch.float32).double().mean())
+            if self.ex.drop_table is not None:
+                # the fraction of (block, sample) residual branches the last step kept, over the blocks that drop
+                rows = [b for b, p in enumerate(self.ex.drop_rates) if p > 0]
+                m["drop_path_kept"] = float((self.ex.drop_table[rows] != 0).double().mean())
             gs = self.ex.grad_guard_stats()
             if gs is not None:
                 # the last step's global gradient norm and clip factor, and the running counts of

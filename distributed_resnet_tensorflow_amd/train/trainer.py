@@ -47,7 +47,8 @@ def model_spec_from_flags(FLAGS):
     width = FLAGS.width_multiplier if model == "wide_resnet" else 1
     return build_spec(ds, FLAGS.resnet_size, model=model, width=width, cardinality=FLAGS.cardinality,
                       width_per_group=FLAGS.width_per_group, se_ratio=getattr(FLAGS, "se_ratio", 0),
-                      avg_down=bool(getattr(FLAGS, "avg_down", False)))
+                      avg_down=bool(getattr(FLAGS, "avg_down", False)),
+                      drop_path_rate=float(getattr(FLAGS, "drop_path_rate", 0.0)))
 
 
 def _meta(FLAGS, spec):
@@ -62,6 +63,8 @@ def _meta(FLAGS, spec):
             **({"se_ratio": FLAGS.se_ratio} if getattr(FLAGS, "se_ratio", 0) else {}),
             # ResNet-D shortcuts only (absent = False)
             **({"avg_down": True} if getattr(FLAGS, "avg_down", False) else {}),
+            # stochastic depth only (absent = 0)
+            **({"drop_path_rate": FLAGS.drop_path_rate} if getattr(FLAGS, "drop_path_rate", 0.0) else {}),
             "optimizer": FLAGS.optimizer, "eta": FLAGS.lars_eta, "eps": FLAGS.lars_eps,
             "adam_beta1": FLAGS.adam_beta1, "adam_beta2": FLAGS.adam_beta2, "adam_eps": FLAGS.adam_epsilon,
             "label_smoothing": FLAGS.label_smoothing, "ema_decay": FLAGS.ema_decay,
@@ -88,6 +91,15 @@ def make_mix_sampler(FLAGS, ex, cluster):
                       seed=FLAGS.seed, rank=cluster.rank)
 
 
+def make_drop_sampler(FLAGS, ex, cluster):
+    """The DropPathSampler of a training feeder (None without stochastic depth); like the mix sampler's, its
+    rank is the cluster rank: every data-parallel replica draws for its own shard."""
+    if ex.drop_table is None:
+        return None
+    from ..data.drop_path import DropPathSampler
+    return DropPathSampler(ex.N, ex.drop_rates, seed=FLAGS.seed, rank=cluster.rank)
+
+
 def make_feeder(FLAGS, ex, cluster, is_training: bool, data_state=None, batch=None, preprocessing=None):
     """preprocessing: the ImageNet input pipeline in place of --imagenet_preprocessing (the evaluators pass
     what the checkpoint's .meta records)."""
@@ -96,6 +108,8 @@ def make_feeder(FLAGS, ex, cluster, is_training: bool, data_state=None, batch=No
     # (training feeders only: evaluation never mixes)
     mix = dict(mix=make_mix_sampler(FLAGS, ex, cluster), mix_index=int(ds.get("mix_batch", 0))) \
         if is_training and mixing(FLAGS) else {}
+    if is_training and ex.drop_table is not None:   # (evaluation never drops)
+        mix = dict(mix, drop=make_drop_sampler(FLAGS, ex, cluster), drop_index=int(ds.get("drop_batch", 0)))
     if FLAGS.synthetic_data:
         return SyntheticFeeder(ex, seed=FLAGS.seed + 101 * cluster.rank, **mix)
     gpu = ex.device.type == "cuda"
