@@ -281,6 +281,35 @@ DRN_API int drn_box_preprocess_jitter(const uint8_t* in, int64_t nbytes, const v
   return (int)hipGetLastError();
 }
 
+// The first launch of drn_box_preprocess_jitter alone: the resampled, flipped fp32 pixels go to scratch (and
+// the gray partial sums to partial) for a consumer other than box_color_kernel (randaug.hip).
+DRN_API int drn_box_resample_scratch(const uint8_t* in, int64_t nbytes, const void* desc, void* scratch, void* partial,
+                                     int N, int OH, int OW, int force_direct, hipStream_t s) {
+  if (in == nullptr || desc == nullptr || scratch == nullptr || partial == nullptr || N < 1 || N > 65535 || OH < 1 ||
+      OW < 1 || OH > 16384 || OW > 16384 || nbytes < 0 || (uintptr_t)in % 4 != 0 || (uintptr_t)scratch % 16 != 0 ||
+      (uintptr_t)partial % 4 != 0 || (uintptr_t)desc % 8 != 0)
+    return (int)hipErrorInvalidValue;
+  const int tx = (OW + drn::TS - 1) / drn::TS, ty = (OH + drn::TS - 1) / drn::TS;
+  drn::launch(drn::box_resample_kernel<true>, dim3(tx * ty, N), dim3(256), 0, s, in, nbytes,
+              (const drn::BoxDesc*)desc, (uint4*)nullptr, (float4*)scratch, (float*)partial, OH, OW, tx,
+              drn::BoxNorm{}, force_direct);
+  return (int)hipGetLastError();
+}
+
+// The second launch of drn_box_preprocess_jitter alone (scripts/randaug_cost.py times it beside randaug.hip).
+DRN_API int drn_box_color(const void* scratch, const void* partial, const void* desc, void* out, int N, int OH, int OW,
+                          float m0, float m1, float m2, float s0, float s1, float s2, hipStream_t s) {
+  if (scratch == nullptr || partial == nullptr || desc == nullptr || out == nullptr || N < 1 || N > 65535 || OH < 1 ||
+      OW < 1 || OH > 16384 || OW > 16384 || (uintptr_t)out % 16 != 0 || (uintptr_t)scratch % 16 != 0 ||
+      (uintptr_t)partial % 4 != 0 || (uintptr_t)desc % 8 != 0)
+    return (int)hipErrorInvalidValue;
+  const float ms[6] = {m0, m1, m2, s0, s1, s2};
+  drn::launch(drn::box_color_kernel, dim3((OH * OW + 255) / 256, N), dim3(256), 0, s, (const float4*)scratch,
+              (const float*)partial, (const drn::BoxDesc*)desc, (uint4*)out, OH * OW,
+              ((OW + drn::TS - 1) / drn::TS) * ((OH + drn::TS - 1) / drn::TS), drn::box_norm(ms));
+  return (int)hipGetLastError();
+}
+
 DRN_API int drn_box_tiles(int OH, int OW) {
   return ((OW + drn::TS - 1) / drn::TS) * ((OH + drn::TS - 1) / drn::TS);
 }

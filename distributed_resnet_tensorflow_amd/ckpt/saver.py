@@ -186,6 +186,8 @@ class Saver:
         meta["imagenet_preprocessing"] = str(meta.get("imagenet_preprocessing", "vgg"))
         meta["rrc_scale_min"] = float(meta.get("rrc_scale_min", 0.08))
         meta["color_jitter"] = float(meta.get("color_jitter", 0.0))
+        meta["rand_augment_layers"] = int(meta.get("rand_augment_layers", 0))   # absent = no RandAugment
+        meta["rand_augment_magnitude"] = int(meta.get("rand_augment_magnitude", 9))
         # the optimizer: absent = the reference's momentum; Adam's constants at the flag defaults
         meta["optimizer"] = str(meta.get("optimizer", "momentum"))
         meta["adam_beta1"] = float(meta.get("adam_beta1", 0.9))

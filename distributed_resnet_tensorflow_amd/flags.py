@@ -209,6 +209,19 @@ def validate(fv: "FlagValues") -> None:
             raise FlagsError("--imagenet_preprocessing=inception / --color_jitter are not supported by --model=lrnet")
     if fv.color_jitter > 0 and fv.imagenet_preprocessing != "inception":
         raise FlagsError("--color_jitter > 0 needs --imagenet_preprocessing=inception")
+    if not 0 <= fv.rand_augment_layers <= 4:
+        raise FlagsError(f"--rand_augment_layers must be 0 (off) or 1..4, got {fv.rand_augment_layers!r}")
+    if not 0 <= fv.rand_augment_magnitude <= 30:
+        raise FlagsError(f"--rand_augment_magnitude must be in 0..30, got {fv.rand_augment_magnitude!r}")
+    if fv.rand_augment_layers > 0:
+        if fv.dataset in ("cifar10", "cifar100"):
+            raise FlagsError(f"--rand_augment_layers is an ImageNet input option: not supported with "
+                             f"--dataset={fv.dataset}")
+        if fv.imagenet_preprocessing != "inception":
+            raise FlagsError("--rand_augment_layers > 0 needs --imagenet_preprocessing=inception")
+        if fv.color_jitter > 0:
+            raise FlagsError("--rand_augment_layers > 0 cannot be combined with --color_jitter > 0: RandAugment's "
+                             "Brightness / Color / Contrast take the colour launch's place")
     if fv.model == "resnext":
         if fv.dataset != "imagenet":
             raise FlagsError(f"--model=resnext is an ImageNet network: not supported with --dataset={fv.dataset}")
@@ -372,6 +385,10 @@ def define_reference_flags(flag_values: FlagValues = FLAGS, **defaults) -> FlagV
     Fl("color_jitter", 0.0, "j > 0 (needs --imagenet_preprocessing=inception): brightness, contrast and saturation "
        "factors from U[1 - j, 1 + j], applied unclamped in a random order per training image (0 <= j < 1). 0 = off.",
        fv)
+    I("rand_augment_layers", 0, "n in 1..4 (needs --imagenet_preprocessing=inception, not with --color_jitter): "
+      "RandAugment (Cubuk et al. 2020), n operations per training image drawn uniformly from torchvision's 14, on "
+      "8-bit levels in one HIP kernel that keeps the image in LDS (image side <= 224). 0 = off.", fv)
+    I("rand_augment_magnitude", 9, "--rand_augment_layers: the magnitude bin, 0..30 (31 bins).", fv)
     I("collective_timeout_secs", 600,"Process-group timeout and collective-watchdog limit: a rank whose "
       "gradient exchange stalls this long exits (the launcher restarts the job from its checkpoint).", fv)
     I("fault_inject_step", -1, "Kill this process at the given global step (fault-injection tests).", fv)

@@ -224,6 +224,15 @@ _SIGS = {
     "drn_box_preprocess": ([c_p, c_i64, c_p, c_p, c_int, c_int, c_int] + [c_f] * 6 + [c_int, c_p], c_int),
     "drn_box_preprocess_jitter": ([c_p, c_i64, c_p, c_p, c_p, c_p, c_int, c_int, c_int] + [c_f] * 6 + [c_int, c_p],
                                   c_int),
+    # the two launches of drn_box_preprocess_jitter on their own: in, nbytes, desc, scratch, partial, N, OH, OW,
+    # force_direct, stream | scratch, partial, desc, out, N, OH, OW, mean x 3, std x 3, stream
+    "drn_box_resample_scratch": ([c_p, c_i64, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_p], c_int),
+    "drn_box_color": ([c_p, c_p, c_p, c_p, c_int, c_int, c_int] + [c_f] * 6 + [c_p], c_int),
+    # RandAugment (randaug.hip): scratch, desc, out, slab, N, O, mean x 3, std x 3, stream
+    "drn_randaug": ([c_p, c_p, c_p, c_p, c_int, c_int] + [c_f] * 6 + [c_p], c_int),
+    "drn_randaug_slab_bytes": ([c_int], c_int),
+    "drn_randaug_max_side": ([], c_int),
+    "drn_randaug_desc_size": ([], c_int),
     "drn_box_tiles": ([c_int, c_int], c_int),
     "drn_box_desc_size": ([], c_int),
     "drn_p2p_signal": ([c_p, c_int, c_p], c_int),

@@ -14,7 +14,8 @@ Op contract (NHWC activations, KRSC conv weights, fp32 statistics):
   bn_bwd_reduce / bn_finalize_bwd / bn_bwd_apply
   pool_bnrelu, sgemm, softmax_xent(_ex, _mix), colsum, maxpool_fwd/bwd, sgd_momentum, weight_tflip
   mix_pairs(src, dst, table)                                 Mixup / CutMix of a batch with its reversal
-  box_preprocess(packed, desc, out, mean, std, jitter)       Inception-style input: box resample, colour jitter
+  box_preprocess(packed, desc, out, mean, std, jitter, randaug=)   Inception-style input: box resample, colour
+                                                             jitter or a RandAugment chain per image
   grad_guard(g, grad_scale, clip, guard, skip_in, ws, rec)   global-norm clip + non-finite step guard
   se_squeeze / se_gate_fwd / se_excite / se_gate_bwd / se_gate_wgrad / se_scale_bwd   Squeeze-and-Excitation gate
   drop_path_fwd(u, shortcut, f, out, stats) / drop_path_bwd(d_out, f, du)   stochastic depth, f per sample
@@ -1458,30 +1459,71 @@ class HipBackend(_Common):
                                              float(means[0]), float(means[1]), float(means[2]), self.stream()),
                    "drn_vgg_preprocess")
 
-    def box_preprocess(self, packed_u8, desc, out, mean, std, jitter=False, force_direct=False):
+    def _box_workspace(self, N, OH, OW, device):
+        """(fp32 scratch copy, gray partial sums) of the two-launch forms of box_preprocess."""
+        key = (N, OH, OW, device)
+        ws = getattr(self, "_box_ws", None)
+        if ws is None or ws[0] != key:
+            ws = (key, torch.empty(N * OH * OW, 4, dtype=torch.float32, device=device),
+                  torch.empty(N * self.L.drn_box_tiles(OH, OW), dtype=torch.float32, device=device))
+            self._box_ws = ws
+        return ws[1], ws[2]
+
+    def randaug(self, scratch, ra_desc, out, mean, std):
+        """RandAugment (csrc/kernels/randaug.hip) on scratch [N * O * O, 4] fp32 pixels on [0, 1] with N
+        RA_DESC records (data/randaug.py; raw bytes on the device) -> out [N, O, O, 8] bf16: quantised to
+        8-bit levels, the records' operation chains, mean / std. One workgroup per image with the image in
+        LDS: a side above 224 is a ValueError."""
+        N, OH, OW, C = out.shape
+        assert C == 8 and out.dtype == torch.bfloat16 and out.is_contiguous(), "randaug: out is NHWC8 bf16"
+        if OH != OW or OH > self.L.drn_randaug_max_side():
+            raise ValueError(f"randaug keeps a square image of side <= {self.L.drn_randaug_max_side()} in LDS, "
+                             f"got {OH} x {OW}")
+        assert scratch.dtype == torch.float32 and scratch.is_contiguous() and scratch.numel() >= N * OH * OW * 4
+        assert ra_desc.numel() * ra_desc.element_size() >= N * self.L.drn_randaug_desc_size(), \
+            "randaug: ra_desc holds N 144-byte records"
+        key = (N, OH, out.device)
+        slab = getattr(self, "_ra_slab", None)
+        if slab is None or slab[0] != key:
+            slab = (key, torch.empty(N * self.L.drn_randaug_slab_bytes(OH), dtype=torch.uint8, device=out.device))
+            self._ra_slab = slab
+        ms = [float(v) for v in tuple(mean) + tuple(std)]
+        _lib.check(self.L.drn_randaug(scratch.data_ptr(), ra_desc.data_ptr(), out.data_ptr(), slab[1].data_ptr(),
+                                      N, OH, *ms, self.stream()), "drn_randaug")
+
+    def box_preprocess(self, packed_u8, desc, out, mean, std, jitter=False, force_direct=False, randaug=None):
         """Inception-style input (csrc/kernels/input_box.hip): packed decoded uint8 batch + N BOX_DESC
         records (raw bytes, on the device) -> out [N, OH, OW, 8] bf16, the box of every image resampled
         with the anti-aliased triangle filter, flipped and normalised with mean / std. jitter=True also
         applies the records' colour factors (a second launch over an fp32 copy kept by the backend);
-        force_direct takes the direct-tap path for every tile (tests)."""
+        force_direct takes the direct-tap path for every tile (tests). randaug (N RA_DESC records, raw
+        bytes on the device): the resample writes the fp32 copy and `randaug` takes the place of the colour
+        launch; not together with jitter."""
         N, OH, OW, C = out.shape
         assert C == 8 and out.dtype == torch.bfloat16 and out.is_contiguous(), "box_preprocess: out is NHWC8 bf16"
         assert packed_u8.dtype == torch.uint8 and packed_u8.is_contiguous()
         assert desc.numel() * desc.element_size() >= N * 64, "box_preprocess: desc holds N 64-byte records"
         ms = [float(v) for v in tuple(mean) + tuple(std)]
+        if randaug is not None:
+            if jitter:
+                raise ValueError("box_preprocess: jitter=True cannot be combined with randaug")
+            if OH != OW or OH > self.L.drn_randaug_max_side():
+                raise ValueError(f"randaug keeps a square image of side <= {self.L.drn_randaug_max_side()} in LDS, "
+                                 f"got {OH} x {OW}")
+            scratch, partial = self._box_workspace(N, OH, OW, out.device)
+            _lib.check(self.L.drn_box_resample_scratch(packed_u8.data_ptr(), packed_u8.numel(), desc.data_ptr(),
+                                                       scratch.data_ptr(), partial.data_ptr(), N, OH, OW,
+                                                       int(force_direct), self.stream()), "drn_box_resample_scratch")
+            self.randaug(scratch, randaug, out, mean, std)
+            return
         if not jitter:
             _lib.check(self.L.drn_box_preprocess(packed_u8.data_ptr(), packed_u8.numel(), desc.data_ptr(),
                                                  out.data_ptr(), N, OH, OW, *ms, int(force_direct), self.stream()),
                        "drn_box_preprocess")
             return
-        key = (N, OH, OW, out.device)
-        ws = getattr(self, "_box_ws", None)
-        if ws is None or ws[0] != key:
-            ws = (key, torch.empty(N * OH * OW, 4, dtype=torch.float32, device=out.device),
-                  torch.empty(N * self.L.drn_box_tiles(OH, OW), dtype=torch.float32, device=out.device))
-            self._box_ws = ws
+        scratch, partial = self._box_workspace(N, OH, OW, out.device)
         _lib.check(self.L.drn_box_preprocess_jitter(packed_u8.data_ptr(), packed_u8.numel(), desc.data_ptr(),
-                                                    out.data_ptr(), ws[1].data_ptr(), ws[2].data_ptr(), N, OH, OW,
+                                                    out.data_ptr(), scratch.data_ptr(), partial.data_ptr(), N, OH, OW,
                                                     *ms, int(force_direct), self.stream()),
                    "drn_box_preprocess_jitter")
 
@@ -2095,10 +2137,19 @@ class RefBackend(_Common):
                                                                   int(r["cx"]), int(r["flip"]), OH))
         out.copy_(res)
 
-    def box_preprocess(self, packed_u8, desc, out, mean, std, jitter=False, force_direct=False):
-        """HipBackend.box_preprocess's contract: data.imagenet.box_preprocess_np (fp64) per image."""
+    def box_preprocess(self, packed_u8, desc, out, mean, std, jitter=False, force_direct=False, randaug=None):
+        """HipBackend.box_preprocess's contract: data.imagenet.box_preprocess_np (fp64) per image; with randaug
+        (N RA_DESC records) the resampled pixels are quantised and go through data.randaug.randaug_np."""
         from ..data.imagenet import BOX_DESC, box_preprocess_np
         N, OH, OW, _ = out.shape
+        if randaug is not None:
+            from ..data import randaug as ra
+            if jitter:
+                raise ValueError("box_preprocess: jitter=True cannot be combined with randaug")
+            if OH != OW or OH > ra.MAX_SIDE:
+                raise ValueError(f"randaug takes a square image of side <= {ra.MAX_SIDE}, got {OH} x {OW}")
+            rd = randaug if isinstance(randaug, np.ndarray) else randaug.cpu().numpy()
+            rd = rd.view(ra.RA_DESC).reshape(-1) if rd.dtype != ra.RA_DESC else rd
         d = desc if isinstance(desc, np.ndarray) else desc.cpu().numpy()
         d = d.view(BOX_DESC).reshape(-1) if d.dtype != BOX_DESC else d
         buf = packed_u8.cpu().numpy() if hasattr(packed_u8, "cpu") else packed_u8
@@ -2109,6 +2160,11 @@ class RefBackend(_Common):
             if off < 0 or off + H * W * 3 > buf.size:
                 raise ValueError(f"box_preprocess: image {i} does not lie inside the packed buffer")
             img = buf[off:off + H * W * 3].reshape(H, W, 3)
+            if randaug is not None:
+                x = box_preprocess_np(img, r, OH, OW, False, (0.0, 0.0, 0.0), (1.0, 1.0, 1.0))
+                q = ra.randaug_np(ra.quantize_np(x), rd[i])
+                res[i, :, :, :3] = torch.from_numpy(ra.normalize_np(q, mean, std)).to(_DT[0])
+                continue
             res[i, :, :, :3] = torch.from_numpy(box_preprocess_np(img, r, OH, OW, jitter, mean, std)).to(_DT[0])
         out.copy_(res)
 

@@ -14,6 +14,9 @@ kernel reads it. `state()` then carries `mix_batch`, the number of draws consume
 
 Stochastic depth (training feeders given a data.drop_path.DropPathSampler): the batch's factor table is
 drawn and staged the same way and handed to the executor with the batch; `state()` carries `drop_batch`.
+
+RandAugment (training ImagenetFeeders given a data.randaug.RandAugSampler): the batch's RA_DESC records are
+drawn with the loader's batch counter as the key and staged the same way; the preprocess call takes them.
 """
 from __future__ import annotations
 
@@ -266,7 +269,10 @@ class CifarFeeder(_StagedFeeder):
 
 class ImagenetFeeder(_StagedFeeder):
     def __init__(self, ex, loader, is_training: bool, max_bytes: int = 64 << 20, mix=None, mix_index: int = 0,
-                 drop=None, drop_index: int = 0):
+                 drop=None, drop_index: int = 0, randaug=None):
+        """randaug (a data.randaug.RandAugSampler, training feeders of an inception loader only): batch i of the
+        loader gets the sampler's draw i (the loader's own batch counter, so nothing is added to state()),
+        staged with the batch's other copies and passed to box_preprocess."""
         from ..data import imagenet as inet
         self.inet = inet
         self.loader = loader
@@ -279,6 +285,15 @@ class ImagenetFeeder(_StagedFeeder):
         self.d_lab = torch.empty(ex.N, dtype=torch.int32, device=ex.device)
         self.h_packed = None  # CPU path: the reference backend preprocesses from host memory
         self.h_desc = None
+        # (evaluation is never augmented)
+        self.randaug = randaug if is_training else None
+        if self.randaug is not None and self.preprocessing != "inception":
+            raise ValueError("RandAugment needs an ImageNet loader made with preprocessing='inception'")
+        self._ra_index = int(getattr(loader, "batch_index", 0))
+        self.d_ra, self.h_ra = None, None
+        if self.randaug is not None:
+            from ..data.randaug import RA_DESC
+            self.d_ra = torch.empty(ex.N * RA_DESC.itemsize, dtype=torch.uint8, device=ex.device)
         # (evaluation never mixes and never drops)
         self._init_staging(ex, mix if is_training else None, mix_index, drop if is_training else None, drop_index)
         self._prefetch()
@@ -288,6 +303,12 @@ class ImagenetFeeder(_StagedFeeder):
         n = int(packed.numel() if isinstance(packed, torch.Tensor) else packed.size)
         # a pinned loader hands desc as a raw-byte tensor, labels as an int32 tensor
         desc_bytes = desc if isinstance(desc, torch.Tensor) else desc.view(np.uint8)
+        ra_pairs = []
+        if self.randaug is not None:
+            self.h_ra = self.randaug.draw(self._ra_index)
+            self._ra_index += 1
+            if self.gpu:
+                ra_pairs = [(self.d_ra, torch.from_numpy(self.h_ra.view(np.uint8)).pin_memory())]
         if not self.gpu:
             self.h_packed = packed
             self.h_desc = desc.numpy().view(self.desc_dtype) if isinstance(desc, torch.Tensor) else desc
@@ -310,11 +331,14 @@ class ImagenetFeeder(_StagedFeeder):
             if self._main is not None:
                 self.d_buf.record_stream(self._main)
         self._stage([(self.d_buf[:n], packed), (self.d_desc, desc_bytes), (self.d_lab, labels)]
-                    + self._mix_pairs(labels))
+                    + ra_pairs + self._mix_pairs(labels))
 
     def _consume(self):
         packed, desc = (self.d_buf, self.d_desc) if self.gpu else (self.h_packed, self.h_desc)
-        if self.preprocessing == "inception":
+        if self.preprocessing == "inception" and self.randaug is not None:
+            self.ex.be.box_preprocess(packed, desc, self.ex.images, self.inet.NORM_MEAN, self.inet.NORM_STD,
+                                      jitter=self.jitter, randaug=self.d_ra if self.gpu else self.h_ra)
+        elif self.preprocessing == "inception":
             self.ex.be.box_preprocess(packed, desc, self.ex.images, self.inet.NORM_MEAN, self.inet.NORM_STD,
                                       jitter=self.jitter)
         else:

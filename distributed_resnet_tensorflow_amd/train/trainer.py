@@ -71,7 +71,11 @@ def _meta(FLAGS, spec):
             "mixup_alpha": FLAGS.mixup_alpha, "cutmix_alpha": FLAGS.cutmix_alpha,
             "clip_grad_norm": FLAGS.clip_grad_norm, "skip_nonfinite_grads": FLAGS.skip_nonfinite_grads,
             "imagenet_preprocessing": FLAGS.imagenet_preprocessing, "rrc_scale_min": FLAGS.rrc_scale_min,
-            "color_jitter": FLAGS.color_jitter}
+            "color_jitter": FLAGS.color_jitter,
+            # RandAugment only (absent = off)
+            **({"rand_augment_layers": FLAGS.rand_augment_layers,
+                "rand_augment_magnitude": FLAGS.rand_augment_magnitude}
+               if getattr(FLAGS, "rand_augment_layers", 0) else {})}
 
 
 def mixing(FLAGS) -> bool:
@@ -98,6 +102,16 @@ def make_drop_sampler(FLAGS, ex, cluster):
         return None
     from ..data.drop_path import DropPathSampler
     return DropPathSampler(ex.N, ex.drop_rates, seed=FLAGS.seed, rank=cluster.rank)
+
+
+def make_randaug_sampler(FLAGS, ex, cluster):
+    """The RandAugSampler of a training ImageNet feeder (None with --rand_augment_layers=0); its rank is the
+    cluster rank like the other samplers'."""
+    if not getattr(FLAGS, "rand_augment_layers", 0):
+        return None
+    from ..data.randaug import RandAugSampler
+    return RandAugSampler(ex.N, ex.spec.image_size, FLAGS.rand_augment_layers, FLAGS.rand_augment_magnitude,
+                          seed=FLAGS.seed, rank=cluster.rank)
 
 
 def make_feeder(FLAGS, ex, cluster, is_training: bool, data_state=None, batch=None, preprocessing=None):
@@ -131,6 +145,8 @@ def make_feeder(FLAGS, ex, cluster, is_training: bool, data_state=None, batch=No
                                      preprocessing=preprocessing or FLAGS.imagenet_preprocessing,
                                      scale_min=FLAGS.rrc_scale_min,
                                      color_jitter=FLAGS.color_jitter if is_training else 0.0, **pin)
+    if is_training and getattr(FLAGS, "rand_augment_layers", 0):   # (evaluation is never augmented)
+        mix = dict(mix, randaug=make_randaug_sampler(FLAGS, ex, cluster))
     return ImagenetFeeder(ex, loader, is_training, **mix)
 
 
