@@ -196,4 +196,5 @@ class Saver:
         meta["se_ratio"] = int(meta.get("se_ratio", 0))   # absent = no Squeeze-and-Excitation gate
         meta["avg_down"] = bool(meta.get("avg_down", False))   # absent = strided projection shortcuts
         meta["drop_path_rate"] = float(meta.get("drop_path_rate", 0.0))   # absent = no stochastic depth
+        meta["deep_stem"] = bool(meta.get("deep_stem", False))   # absent = the 7x7 / 2 stem
         return meta

@@ -236,6 +236,8 @@ def validate(fv: "FlagValues") -> None:
         raise FlagsError("--se_ratio is not supported by --model=lrnet")
     if fv.avg_down and fv.model == "lrnet":
         raise FlagsError("--avg_down is not supported by --model=lrnet")
+    if fv.deep_stem and (fv.model == "lrnet" or fv.dataset != "imagenet"):
+        raise FlagsError("--deep_stem is an ImageNet stem and is not supported by --model=lrnet")
     if not 0.0 <= fv.drop_path_rate < 1.0:
         raise FlagsError(f"--drop_path_rate must be in [0, 1), got {fv.drop_path_rate!r}")
     if fv.drop_path_rate > 0 and fv.model == "lrnet":
@@ -318,6 +320,9 @@ def define_reference_flags(flag_values: FlagValues = FLAGS, **defaults) -> FlagV
       "0 = off. Any --model but lrnet.", fv)
     B("avg_down", False, "ResNet-D shortcuts: every stride-2 projection becomes a 2x2 / 2 average pool + a 1x1 "
       "stride-1 conv (same variables). Any --model but lrnet.", fv)
+    B("deep_stem", False, "ResNet-C deep stem: the 7x7 / 2 stem conv becomes conv3x3 / 2 3 -> 32, BN, ReLU, conv3x3 "
+      "32 -> 32, BN, ReLU, conv3x3 32 -> 64 (with --avg_down: ResNet-50-D). ImageNet only; any --model but lrnet.",
+      fv)
     Fl("drop_path_rate", 0.0, "Stochastic depth: training drops block b of B's residual branch per sample with "
        "probability rate * b / (B - 1) and scales the kept ones by 1 / (1 - p); 0 = off. Any --model but lrnet; "
        "not with --se_ratio. Evaluation never drops.", fv)

@@ -52,6 +52,8 @@ def forward(spec: NetSpec, p: Dict[str, torch.Tensor], state: Dict[str, tuple], 
     drop_path: stochastic depth's factor table [blocks][N] (keep / (1 - p) per block and sample) scaling
     each residual branch of a training forward; evaluation never drops."""
     x = images_nhwc[..., :spec.in_channels].to(p[f"{spec.stem.name}/kernel"].dtype).permute(0, 3, 1, 2)
+    for c, b in zip(spec.stem_pre, spec.stem_bns):   # (deep stem: conv, BN, ReLU twice in front of the last conv)
+        x = _bn_relu(_conv(x, p[f"{c.name}/kernel"], c), b, p, state, training)
     x = _conv(x, p[f"{spec.stem.name}/kernel"], spec.stem)
     if spec.maxpool:
         x = _maxpool_same(x)

@@ -109,6 +109,10 @@ class NetSpec:
     final_hw: int = 0
     final_c: int = 0
     dense_name: str = "dense"
+    # ResNet-C deep stem (extension): the convs in front of `stem` (3x3 / 2 3 -> 32, 3x3 / 1 32 -> 32) and the
+    # BatchNorm + ReLU behind each of them; `stem` is then the last conv (3x3 / 1 32 -> 64). Empty: one stem conv
+    stem_pre: List[Conv] = field(default_factory=list)
+    stem_bns: List[BN] = field(default_factory=list)
 
     # -- TF variable inventory, creation order ---------------------------------------------------
     def trainable_variables(self):
@@ -122,6 +126,9 @@ class NetSpec:
             out.append((f"{b.name}/gamma", (b.c,), "gamma", b))
             out.append((f"{b.name}/beta", (b.c,), "beta", b))
 
+        for c, b in zip(self.stem_pre, self.stem_bns):
+            conv(c)
+            bn(b)
         conv(self.stem)
         for blk in self.blocks:
             bn(blk.bn1)
@@ -143,7 +150,7 @@ class NetSpec:
         return out
 
     def batch_norms(self) -> List[BN]:
-        bns = []
+        bns = list(self.stem_bns)
         for blk in self.blocks:
             bns.append(blk.bn1)
             bns.extend(blk.bns)
@@ -151,7 +158,7 @@ class NetSpec:
         return bns
 
     def convs(self) -> List[Conv]:
-        cs = [self.stem]
+        cs = self.stem_pre + [self.stem]
         for blk in self.blocks:
             if blk.proj is not None:
                 cs.append(blk.proj)
@@ -171,7 +178,7 @@ class NetSpec:
         """Multiply-add FLOPs (x2) of one image's forward pass: convs + dense."""
         fl = 0
         hw = self.image_size
-        fl += 2 * self.stem.params * self.stem_hw * self.stem_hw
+        fl += 2 * sum(c.params for c in self.convs()[:len(self.stem_pre) + 1]) * self.stem_hw * self.stem_hw
         for blk in self.blocks:
             if blk.proj is not None:
                 fl += 2 * blk.proj.params * blk.out_hw * blk.out_hw
@@ -298,14 +305,18 @@ IMAGENET_SIZES = {
 
 def imagenet_resnet_v2(resnet_size: int = 50, num_classes: int = 1001, width: int = 1,
                        image_size: int = 224, groups: int = 1, width_per_group: int = 64,
-                       se_ratio: int = 0, avg_down: bool = False, drop_path_rate: float = 0.0) -> NetSpec:
+                       se_ratio: int = 0, avg_down: bool = False, drop_path_rate: float = 0.0,
+                       deep_stem: bool = False) -> NetSpec:
     """imagenet_resnet_v2 (reference resnet_model_official.py:281-366); width=2 -> WRN-50-2 (extension);
     groups > 1 -> ResNeXt (extension): the bottleneck's 3x3 conv is grouped, its width in stage s is
     groups * width_per_group * 2^(s-1) (32x4d: 128 / 256 / 512 / 1024), the block output stays filters * 4.
     se_ratio > 0 -> every block gated by Squeeze-and-Excitation, hidden width max(C / se_ratio, 8) (extension).
     avg_down -> ResNet-D shortcuts (extension): every stride-2 projection becomes a 2x2 / 2 average pool + a 1x1
     stride-1 conv (Block.avg_down); variable names and shapes are unchanged.
-    drop_path_rate > 0 -> stochastic depth (extension): Block.drop_rate by the linear rule; variables unchanged."""
+    drop_path_rate > 0 -> stochastic depth (extension): Block.drop_rate by the linear rule; variables unchanged.
+    deep_stem -> the ResNet-C stem (extension; He et al. 2019, section 4.2): the 7x7 / 2 conv becomes conv3x3 / 2
+    3 -> 32, BN, ReLU, conv3x3 / 1 32 -> 32, BN, ReLU, conv3x3 / 1 32 -> 64 (NetSpec.stem_pre / stem_bns / stem);
+    variables conv2d, batch_normalization, conv2d_1, batch_normalization_1, conv2d_2, then the blocks."""
     if resnet_size not in IMAGENET_SIZES:
         raise ValueError(f"Not a valid resnet_size: {resnet_size}")
     kind, layers = IMAGENET_SIZES[resnet_size]
@@ -315,8 +326,18 @@ def imagenet_resnet_v2(resnet_size: int = 50, num_classes: int = 1001, width: in
         raise ValueError("ResNeXt (groups > 1) needs a bottleneck resnet_size (50, 101, 152, 200) and width 1")
     _check_se_ratio(se_ratio)
     nm = _Namer()
-    stem = Conv(nm.next_conv(), 3, 64, 7, 2, cin_store=8)
-    stem_hw = stem.out_hw(image_size)
+    stem_pre, stem_bns = [], []
+    if deep_stem:
+        if image_size % 2:
+            raise ValueError(f"deep_stem: an odd image size ({image_size}) is not supported")
+        for cin, store, stride in ((3, 8, 2), (32, 32, 1)):
+            stem_pre.append(Conv(nm.next_conv(), cin, 32, 3, stride, cin_store=store))
+            stem_bns.append(BN(nm.next_bn(), 32))
+        stem = Conv(nm.next_conv(), 32, 64, 3, 1)
+        stem_hw = stem_pre[0].out_hw(image_size)
+    else:
+        stem = Conv(nm.next_conv(), 3, 64, 7, 2, cin_store=8)
+        stem_hw = stem.out_hw(image_size)
     pool_hw = (stem_hw + 1) // 2  # max_pooling2d(3, 2, 'SAME')
     tag = f"wide_resnet{resnet_size}_{width}" if width != 1 else f"imagenet_resnet{resnet_size}_v2"
     if groups > 1:
@@ -325,7 +346,10 @@ def imagenet_resnet_v2(resnet_size: int = 50, num_classes: int = 1001, width: in
         tag = "se_" + tag
     if avg_down:
         tag += "_avgdown"
-    spec = NetSpec(tag, "imagenet", num_classes, image_size, 3, stem, stem_hw, True, pool_hw)
+    if deep_stem:
+        tag += "_deepstem"
+    spec = NetSpec(tag, "imagenet", num_classes, image_size, 3, stem, stem_hw, True, pool_hw,
+                   stem_pre=stem_pre, stem_bns=stem_bns)
     c, hw = 64, pool_hw
     for stage, (f, s) in enumerate(((64, 1), (128, 2), (256, 2), (512, 2)), start=1):
         c, hw = _stage(spec, nm, kind, stage, f, layers[stage - 1], s, c, hw, width=width, groups=groups,
@@ -337,22 +361,25 @@ def imagenet_resnet_v2(resnet_size: int = 50, num_classes: int = 1001, width: in
 
 def build_spec(dataset: str, resnet_size: int | None = None, model: str = "resnet", width: int = 1,
                num_classes: int | None = None, cardinality: int = 32, width_per_group: int = 4,
-               se_ratio: int = 0, avg_down: bool = False, drop_path_rate: float = 0.0) -> NetSpec:
+               se_ratio: int = 0, avg_down: bool = False, drop_path_rate: float = 0.0,
+               deep_stem: bool = False) -> NetSpec:
     """Network selection of the reference ResNet wrapper (resnet_model.py:71-74, size fixed to 50
     there; `--resnet_size` makes it selectable here). cifar100 is supported."""
     if model == "wide_resnet":
         width = max(width, 2)
+    if deep_stem and dataset != "imagenet":
+        raise ValueError("deep_stem is an ImageNet stem (the CIFAR nets have a single 3x3 stem conv)")
     if model == "resnext":
         if dataset != "imagenet":
             raise ValueError("model=resnext is an ImageNet network (bottleneck blocks)")
         return imagenet_resnet_v2(resnet_size or 50, num_classes or 1001, groups=cardinality,
                                   width_per_group=width_per_group, se_ratio=se_ratio, avg_down=avg_down,
-                                  drop_path_rate=drop_path_rate)
+                                  drop_path_rate=drop_path_rate, deep_stem=deep_stem)
     if dataset in ("cifar10", "cifar100", "cifar"):
         nc = num_classes or (100 if dataset == "cifar100" else 10)
         return cifar_resnet_v2(resnet_size or 50, nc, se_ratio=se_ratio, avg_down=avg_down,
                                drop_path_rate=drop_path_rate)
     if dataset == "imagenet":
         return imagenet_resnet_v2(resnet_size or 50, num_classes or 1001, width=width, se_ratio=se_ratio,
-                                  avg_down=avg_down, drop_path_rate=drop_path_rate)
+                                  avg_down=avg_down, drop_path_rate=drop_path_rate, deep_stem=deep_stem)
     raise ValueError(f"unknown dataset {dataset}")

@@ -116,6 +116,17 @@ class DrnDropPathArgs(ctypes.Structure):
                [(n, c_int) for n in ("N", "HW", "C", "stats_rep", "S", "pps", "slab", "cpw", "planes", "pad_")]
 
 
+class DrnStemDeepArgs(ctypes.Structure):
+    """Mirror of csrc/kernels/stem_deep.hip `struct DrnStemDeepArgs` (deep-stem 3x3 convs; the entry points
+    fill every field after stats_rep)."""
+    _fields_ = [(n, c_p) for n in ("x", "w", "y", "arg", "scale", "shift", "stats")] + \
+               [(n, c_int) for n in ("N", "H", "W", "C", "K", "stride", "stats_rep",
+                                     "P", "Q", "PP", "QP", "ppad_h", "ppad_w",
+                                     "th", "tw", "tiles_y", "tiles_x", "ntiles", "tpw",
+                                     "cth", "ctw", "ih", "iw", "in_bytes", "pad_")] + \
+               [(n, DrnFastDiv) for n in ("fd_tw", "fd_ctw", "fd_iw", "fd_tx", "fd_txy")]
+
+
 class DrnConvCfgInfo(ctypes.Structure):
     """Mirror of csrc/include/drn_conv.h `struct DrnConvCfgInfo` (drn_conv_cfg_info)."""
     _fields_ = [(n, c_int) for n in ("kind", "bp", "bc", "waves_p", "ns", "nw", "bk", "nh", "il", "ks")]
@@ -161,6 +172,10 @@ _SIGS = {
     "drn_drop_path_bwd": ([ctypes.POINTER(DrnDropPathArgs), c_p], c_int),
     "drn_drop_path_splits": ([c_int, c_int, c_int], c_int),
     "drn_drop_path_args_size": ([], c_int),
+    # deep stem (stem_deep.hip): 3x3 conv with BN + ReLU prologue (+ statistics), the same + 3x3 / 2 max-pool
+    "drn_stem_deep_conv": ([ctypes.POINTER(DrnStemDeepArgs), c_p], c_int),
+    "drn_stem_deep_conv_pool": ([ctypes.POINTER(DrnStemDeepArgs), c_p], c_int),
+    "drn_stem_deep_args_size": ([], c_int),
     "drn_splitk_reduce": ([c_p, c_p, c_i64, c_int, c_f, c_int, c_p], c_int),
     "drn_bn_stats": ([c_p, c_p, c_int, c_int, c_int, c_int, c_p], c_int),
     "drn_bn_finalize": ([c_p, c_int, c_int, c_f, c_p, c_p, c_f, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_p], c_int),
@@ -308,7 +323,8 @@ def lib():
         for name, st in (("drn_bn_fin_size", DrnBnFin), ("drn_conv_args_size", DrnConvFwdArgs),
                          ("drn_wgrad_args_size", DrnConvWgradArgs), ("drn_gconv_args_size", DrnGconvArgs),
                          ("drn_se_args_size", DrnSeArgs), ("drn_pool_proj_args_size", DrnPoolProjArgs),
-                         ("drn_drop_path_args_size", DrnDropPathArgs)):
+                         ("drn_drop_path_args_size", DrnDropPathArgs),
+                         ("drn_stem_deep_args_size", DrnStemDeepArgs)):
             if getattr(h, name)() != ctypes.sizeof(st):
                 raise KernelLibraryError(f"{st.__name__} layout mismatch between Python and {LIB_PATH.name}")
         _check_stamp(h)

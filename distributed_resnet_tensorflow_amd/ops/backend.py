@@ -863,6 +863,53 @@ class HipBackend(_Common):
             a.ws, a.ws_elems = ws.data_ptr(), ws.numel()
         _lib.check(self.L.drn_gconv_wgrad(ctypes.byref(a), self.stream()), "drn_gconv_wgrad")
 
+    # -- deep stem (csrc/kernels/stem_deep.hip) ------------------------------------------------------
+    @staticmethod
+    def stem_deep_check(x_shape, w_shape, stride: int):
+        """Raises unless input x_shape [N,H,W,C] and weights w_shape [K,3,3,C] are inside the deep-stem
+        kernels' domain (needs no device). Returns the conv's output size (P, Q)."""
+        N, H, W, C = x_shape
+        K, R, S, Cw = w_shape
+        if not (R == S == 3 and C == Cw and C in (8, 32) and K in (32, 64) and stride in (1, 2)
+                and N >= 1 and H >= 1 and W >= 1):
+            raise ValueError(f"deep-stem conv outside the HIP kernels' domain (3x3, C in (8, 32), K in (32, 64), "
+                             f"stride 1 or 2): x {tuple(x_shape)}, w {tuple(w_shape)}, stride {stride}")
+        return (H - 1) // stride + 1, (W - 1) // stride + 1
+
+    def _stem_deep_args(self, x, w, y, stride, in_bn, stats, out_hw):
+        if tuple(y.shape) != (x.shape[0],) + tuple(out_hw) + (w.shape[0],):
+            raise ValueError(f"deep-stem conv: output {tuple(y.shape)} for x {tuple(x.shape)}, w {tuple(w.shape)}")
+        self._gconv_tensors(x, w, y)
+        a = _lib.DrnStemDeepArgs()
+        a.N, a.H, a.W, a.C, a.K, a.stride = x.shape[0], x.shape[1], x.shape[2], x.shape[3], w.shape[0], stride
+        a.x, a.w, a.y = x.data_ptr(), w.data_ptr(), y.data_ptr()
+        if in_bn is not None:
+            sc, sh = in_bn
+            assert sc.numel() == sh.numel() == a.C and sc.dtype == sh.dtype == torch.float32
+            a.scale, a.shift = sc.data_ptr(), sh.data_ptr()
+        if stats is not None:
+            assert stats.numel() % (2 * a.K) == 0 and stats.dtype == torch.float32, \
+                "stats accumulator must be fp32 [rep][2][K]"
+            a.stats, a.stats_rep = stats.data_ptr(), stats.numel() // (2 * a.K)
+        return a
+
+    def stem_deep_conv(self, x, w, y, stride, in_bn=None, stats=None):
+        """y = conv3x3(a, w), leading pad 1: a = x, or relu(scale * x + shift) rounded to bf16 with in_bn =
+        (scale, shift), which must be published; padding is zero AFTER the prologue. Optional BN statistics
+        of the stored y."""
+        P, Q = self.stem_deep_check(x.shape, w.shape, stride)
+        a = self._stem_deep_args(x, w, y, stride, in_bn, stats, (P, Q))
+        _lib.check(self.L.drn_stem_deep_conv(ctypes.byref(a), self.stream()), "drn_stem_deep_conv")
+
+    def stem_deep_conv_pool(self, x, w, y, arg, stride, in_bn=None, stats=None):
+        """y, arg = 3x3 / 2 'SAME' max-pool (first maximum, tap byte r * 3 + s: maxpool_bwd's layout) of the
+        bf16-rounded stem_deep_conv output, which is never stored; statistics of the pooled y."""
+        P, Q = self.stem_deep_check(x.shape, w.shape, stride)
+        a = self._stem_deep_args(x, w, y, stride, in_bn, stats, ((P + 1) // 2, (Q + 1) // 2))
+        assert arg.shape == y.shape and arg.dtype == torch.uint8 and arg.is_contiguous() and arg.data_ptr() % 8 == 0
+        a.arg = arg.data_ptr()
+        _lib.check(self.L.drn_stem_deep_conv_pool(ctypes.byref(a), self.stream()), "drn_stem_deep_conv_pool")
+
     # -- ResNet-D pooled projection (csrc/kernels/pool_proj.hip) -----------------------------------
     @staticmethod
     def pool_proj_check(x_shape, sc_shape):
@@ -1667,6 +1714,17 @@ class RefBackend(_Common):
         dw = torch.nn.grad.conv2d_weight(xc, (K, cg, R, S), dy.to(_DT[0]).permute(0, 3, 1, 2), stride=stride,
                                          groups=K // cg)
         out.copy_(dw.permute(0, 2, 3, 1))
+
+    # deep stem: the HIP contract (3x3, leading pad 1, zero padding AFTER the prologue) for any width
+    def stem_deep_conv(self, x, w, y, stride, in_bn=None, stats=None):
+        self._conv_fwd(x, w, y, ConvGeom(stride, 1, 1, 1), in_bn=in_bn, stats=stats)
+
+    def stem_deep_conv_pool(self, x, w, y, arg, stride, in_bn=None, stats=None):
+        P, Q = (x.shape[1] - 1) // stride + 1, (x.shape[2] - 1) // stride + 1
+        conv = torch.empty(x.shape[0], P, Q, w.shape[0], dtype=y.dtype, device=y.device)
+        self._conv_fwd(x, w, conv, ConvGeom(stride, 1, 1, 1), in_bn=in_bn)
+        pad_h, pad_w = (max((n - 1) * 2 + 3 - m, 0) // 2 for n, m in ((y.shape[1], P), (y.shape[2], Q)))
+        self.maxpool_fwd(conv, y, arg, 3, 2, pad_h, pad_w, stats=stats)
 
     # ResNet-D pooled projection: the HIP contract (csrc/kernels/pool_proj.hip), the stash included
     def pool_proj_fwd(self, x, w, sc, ap, in_bn=None):

@@ -95,10 +95,10 @@ def _stamp_object() -> Path:
 # forms off: the MI355X pool this library is checked on asks that of HIP code added to it. Without
 # the flag hipcc emits 8 v_pk_add_f32 / v_pk_mul_f32 in that file (the statistics sums); with it
 # their scalar forms, at no measurable cost. The older translation units are built as before.
-# se.hip, pool_proj.hip, drop_path.hip and randaug.hip (added after it) likewise.
+# se.hip, pool_proj.hip, drop_path.hip, randaug.hip and stem_deep.hip (added after it) likewise.
 _NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 SOURCE_FLAGS = {"conv_group.hip": _NO_PK_F32, "se.hip": _NO_PK_F32, "pool_proj.hip": _NO_PK_F32,
-                "drop_path.hip": _NO_PK_F32, "randaug.hip": _NO_PK_F32}
+                "drop_path.hip": _NO_PK_F32, "randaug.hip": _NO_PK_F32, "stem_deep.hip": _NO_PK_F32}
 
 
 def _compile(src: Path, extra: list[str], obj_dir: Optional[Path] = None, include: Path = INCLUDE) -> Path:

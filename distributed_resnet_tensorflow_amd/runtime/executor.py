@@ -375,7 +375,7 @@ class Executor:
             # grouped 3x3 (ResNeXt): csrc/kernels/conv_group.hip gathers its data-gradient fragments from
             # the forward weights, so there is no flipped copy to refresh; one launch writes all of dX
             pass
-        elif c is not self.spec.stem:
+        elif c is not self.spec.convs()[0]:   # (the network's first conv has no data gradient)
             if c.stride == 1:
                 wt_descs.append(tflip_desc(s.offset, wt_off, K, R, R, C))
                 phases.append(DgradPhase((C, R, R, K), wt_off, dgrad_geom(g, R, R), None))
@@ -407,7 +407,7 @@ class Executor:
         """(rows, channels) of every statistics accumulator the plan allocates (upper bound)."""
         sp, N = self.spec, self.N
         hs = sp.stem_hw
-        out = [(N * hs * hs, sp.stem.cout)]
+        out = [(N * hs * hs, sp.stem.cout)] + [(N * hs * hs, b.c) for b in sp.stem_bns]
         if sp.maxpool:
             out.append((N * sp.pool_hw * sp.pool_hw, sp.stem.cout))
         for blk in sp.blocks:
@@ -446,14 +446,15 @@ class Executor:
 
     def all_bn_states(self) -> List[BNState]:
         """Every BatchNorm of the network in TF creation order."""
-        return [b for bp in self.blocks for b in bp.bn] + [self.final_bn]
+        return self.stem_bn + [b for bp in self.blocks for b in bp.bn] + [self.final_bn]
 
     def _alloc(self):
         sp, N = self.spec, self.N
         be = self.be
         # one arena for every BN statistics accumulator (forward sums and backward sums), cleared
         # by a single fill at the start of each training step
-        all_c = [b.c for blk in sp.blocks for b in [blk.bn1] + list(blk.bns)] + [sp.final_bn.c, sp.stem.cout]
+        all_c = [b.c for blk in sp.blocks for b in [blk.bn1] + list(blk.bns)] + [sp.final_bn.c, sp.stem.cout] + \
+            [b.c for b in sp.stem_bns]
         self.stats_rep = int(getattr(be, "stats_replicas", 1))
         if self.deterministic:
             arena = 64 + sum(2 * ((2 * c * self._det_replicas(m, c) + 15) // 16 * 16) for m, c in self._bn_shapes())
@@ -463,7 +464,24 @@ class Executor:
         self.stats_arena = self._f32(arena)
         self._arena_off = 0
         wt_descs, wt_off = [], 0
-        self.stem_op, wt_off = self._conv_op(sp.stem, wt_descs, wt_off)
+        # (in_hw: the deep stem's last conv reads the 112 x 112 tensor; the single stem conv has no data gradient)
+        self.stem_op, wt_off = self._conv_op(sp.stem, wt_descs, wt_off, in_hw=sp.stem_hw if sp.stem_pre else 0)
+        # Deep stem (spec.stem_pre: conv3x3 / 2 3 -> 32, conv3x3 / 1 32 -> 32 in front of stem_op, now 3x3 / 1
+        # 32 -> 64, a BatchNorm + ReLU behind each of the two). Fused (the default; csrc/kernels/stem_deep.hip):
+        # three launches, each conv applying its producer's BatchNorm while it stages its input and the last
+        # one pooling its own output, so neither BatchNorm is materialised and the 64-channel conv output is
+        # never stored. DRN_DEEP_STEM_FUSED=0: composed from the dense kernels (conv, bn_apply, conv, bn_apply,
+        # conv, maxpool_fwd), the measurement baseline. The backward is composed from existing kernels either
+        # way (_deep_stem_bwd). Without stem_pre nothing below is allocated
+        self.deep = bool(sp.stem_pre)
+        self.deep_fused = self.deep and os.environ.get("DRN_DEEP_STEM_FUSED", "1") != "0"
+        self.stem_pre_ops: List[ConvOp] = []
+        self.stem_bn: List[BNState] = []
+        for c, hw in zip(sp.stem_pre, (sp.image_size, sp.stem_hw)):
+            op, wt_off = self._conv_op(c, wt_descs, wt_off, in_hw=hw)
+            self.stem_pre_ops.append(op)
+            if self.is_hip and self.deep_fused:
+                be.stem_deep_check((N, hw, hw, c.cin_store), op.w.shape, c.stride)
         # the stem's weights lead the flat parameter buffer: [0, _stem_hi) is the slice the
         # optimizer updates last when backward(defer_tail=True) (0: layout differs, no deferral)
         self._stem_hi = int(self.stem_op.dw.numel()) if self.stem_op.grad_lo == 0 else 0
@@ -472,13 +490,13 @@ class Executor:
         # update only adds a launch to its launch-bound graph
         stem_macs = N * sp.stem_hw * sp.stem_hw * sp.stem.cout * sp.stem.k * sp.stem.k * sp.stem.cin_store
         mode = os.environ.get("DRN_DEFER_TAIL", "auto")
-        if mode == "0" or (mode == "auto" and stem_macs < 1e9):
-            self._stem_hi = 0
+        if mode == "0" or (mode == "auto" and stem_macs < 1e9) or self.deep:
+            self._stem_hi = 0   # (deep stem: three weight gradients end the step, nothing is deferred)
         self._tail_ev = None
         self._stem_ev = None   # side stream: the stem's weight gradient (issued last) is done
         self._tflip_ev = None  # side stream: the data-gradient weights of the next backward are ready
         img = sp.image_size
-        self.images = self._act(N, img, img, sp.stem.cin_store)
+        self.images = self._act(N, img, img, sp.convs()[0].cin_store)
         # Packed stem (csrc/kernels/stem.hip, on the HIP backend): the 7x7/2 stem over
         # RGB runs on a 4-channel copy of the images with a zero pixel column on each side and on
         # weights padded to 8 taps per row, so one 16-byte piece is a tap PAIR: 4 forward k-stages
@@ -510,8 +528,17 @@ class Executor:
                           and c0.cout % 32 == 0 and sp.pool_hw == (hs + 1) // 2
                           and max((sp.pool_hw - 1) * 2 + 3 - hs, 0) // 2 == 0 and 0 <= self.stem_geom4.pad_w <= 2 and self.stem_geom4.pad_h <= 3
                           and os.environ.get("DRN_STEM_POOL", "1") == "1")
-        self.stem_out = self._act(N, hs, hs, sp.stem.cout)
+        # (the fused deep stem never stores the last conv's output)
+        self.stem_out_shape = (N, hs, hs, sp.stem.cout)
+        self.stem_out = None if self.deep_fused else self._act(*self.stem_out_shape)
         max_act = N * hs * hs * sp.stem.cout
+        for b in sp.stem_bns:
+            st = self._bn_state(b)
+            st.stats, st.G = self._stats_for(N * hs * hs, b.c)
+            st.rows, st.src = N * hs * hs, self._act(N, hs, hs, b.c)
+            if not self.deep_fused:
+                st.act = self._act(N, hs, hs, b.c)
+            self.stem_bn.append(st)
         max_bn_part = 0
         if sp.maxpool:
             ph = sp.pool_hw
@@ -530,7 +557,7 @@ class Executor:
             # the raw branch u of the block being computed: dead once the add has run, so one buffer serves all
             self.drop_u = self._act(max(N * blk.out_hw * blk.out_hw * blk.out_c
                                         for blk, p in zip(sp.blocks, self.drop_rates) if p > 0))
-        ws_need = be.wgrad_ws_elems(N * hs * hs, sp.stem.cout, sp.stem.k, sp.stem.k, sp.stem.cin_store)
+        ws_need = max(be.wgrad_ws_elems(N * hs * hs, c.cout, c.k, c.k, c.cin_store) for c in sp.stem_pre + [sp.stem])
         if self.stem_pack:  # the packed stem's gradient has fewer k-tiles, so it may take more splits
             ws_need = max(ws_need, be.wgrad_ws_elems(N * hs * hs, *self.stem_dw4.shape))
         for blk in sp.blocks:
@@ -613,7 +640,7 @@ class Executor:
                 if grouped or self.bn_policy == "all" or (self.bn_policy == "1x1" and big and
                                                           not all(fusable(c) for c in consumers)):
                     b.act = self._act(*b.src.shape)
-        for b in [b for bp in self.blocks for b in bp.bn] + [self.final_bn]:
+        for b in [b for bp in self.blocks for b in bp.bn] + [self.final_bn] + self.stem_bn:
             b.bacc, b.bG = self._stats_for(b.rows, b.bn.c)
         self.last_out = x
         C, ncls = sp.final_c, sp.num_classes
@@ -705,6 +732,7 @@ class Executor:
 
     def _all_ops(self):
         yield self.stem_op
+        yield from self.stem_pre_ops
         for bp in self.blocks:
             yield from bp.convs
             if bp.proj is not None:
@@ -764,8 +792,10 @@ class Executor:
         b.cfin_pub = False
         return self._fin_fwd_spec(b, publish=True)
 
-    def _bn_fwd(self, b: BNState, train: bool):
-        if train and self.cfin and b is not self.final_bn:
+    def _bn_fwd(self, b: BNState, train: bool, own_launch: bool = False):
+        """own_launch: the consumer reads PUBLISHED scale / shift (the fused deep-stem convs), so the small
+        finalize launch runs whatever the consumer-side rules would choose."""
+        if train and self.cfin and b is not self.final_bn and not own_launch:
             if b.act is not None:  # materialised for a 3x3 consumer: the apply finalizes
                 self.be.bn_apply_fin(b.src, b.act, self._fin_fwd_spec(b, publish=True), relu=True)
             else:
@@ -792,7 +822,9 @@ class Executor:
         if train:
             be.zero_(self.stats_arena)
         st = self.stem_op
-        if self.stem_pool:
+        if self.deep:
+            self._deep_stem_fwd(train)
+        elif self.stem_pool:
             # conv + max-pool + the pooled BN statistics in one kernel: the conv output never
             # reaches HBM (csrc/kernels/stem_pool.hip stem_conv_pool_kernel)
             be.stem_pack_input(self.images, self.stem_xp)
@@ -808,7 +840,7 @@ class Executor:
                         stats=self.stem_stats if train else None)
         else:
             be.conv_fwd(self.images, st.w, self.stem_out, st.geom, stats=self.stem_stats if train else None)
-        if sp.maxpool and not self.stem_pool:
+        if sp.maxpool and not self.stem_pool and not self.deep_fused:
             ph = sp.pool_hw
             pad = max((ph - 1) * 2 + 3 - sp.stem_hw, 0) // 2
             # the first block's BN statistics come out of the pooling kernel itself (the
@@ -843,6 +875,54 @@ class Executor:
                                correct_k=self.correct_k)
         if self.check_nan:
             self._check(self.loss_vec, "cross-entropy")
+
+    def _deep_stem_fwd(self, train: bool):
+        """images -> conv2d -> BN ReLU -> conv2d_1 -> BN ReLU -> conv2d_2 (-> max-pool when fused; the composed
+        path leaves stem_out to forward()'s pooling)."""
+        be = self.be
+        (op0, op1), op2, (b0, b1) = self.stem_pre_ops, self.stem_op, self.stem_bn
+        if self.deep_fused:
+            be.stem_deep_conv(self.images, op0.w, b0.src, op0.conv.stride, stats=b0.stats if train else None)
+            self._bn_fwd(b0, train, own_launch=True)
+            be.stem_deep_conv(b0.src, op1.w, b1.src, 1, in_bn=b0.ss, stats=b1.stats if train else None)
+            self._bn_fwd(b1, train, own_launch=True)
+            # (the pooled statistics are added once per workgroup: the deterministic mode's too)
+            be.stem_deep_conv_pool(b1.src, op2.w, self.pool_out, self.pool_arg, 1, in_bn=b1.ss,
+                                   stats=self.pool_stats if train else None)
+            return
+        be.conv_fwd(self.images, op0.w, b0.src, op0.geom, stats=b0.stats if train else None)
+        self._bn_fwd(b0, train)
+        be.conv_fwd(b0.act, op1.w, b1.src, op1.geom, stats=b1.stats if train else None)
+        self._bn_fwd(b1, train)
+        be.conv_fwd(b1.act, op2.w, self.stem_out, op2.geom)
+
+    def _deep_stem_bwd(self, bufs, cur: int):
+        """bufs[cur] holds d(pool_out). maxpool_bwd, then per BatchNorm the consumer's weight gradient (side
+        stream), its dense data gradient on flipped weights with the fused ReLU-mask + BN-backward sums, and
+        bn_bwd_apply; the first conv's weight gradient last. The weight gradients read the materialised
+        activations (composed forward) or recompute them in their BN prologue (fused forward)."""
+        be, sp = self.be, self.spec
+        (op0, op1), op2, (b0, b1) = self.stem_pre_ops, self.stem_op, self.stem_bn
+        if len(self._lru) != len(bufs):
+            self._lru = list(range(len(bufs)))
+        d_x0 = self._view(bufs[cur], self.pool_out)
+        dy_k = self._take(bufs, (cur,))
+        self._claim(bufs[dy_k])
+        dy = bufs[dy_k][:self.N * sp.stem_hw ** 2 * sp.stem.cout].view(self.stem_out_shape)
+        pad = max((sp.pool_hw - 1) * 2 + 3 - sp.stem_hw, 0) // 2
+        be.maxpool_bwd(d_x0, self.pool_arg, dy, 3, 2, pad, pad)
+        for op, b in ((op2, b1), (op1, b0)):
+            a_in, pro = (b.act, None) if b.act is not None else (b.src, b.ss)
+            self._wgrad(a_in, dy, op.dw, op.geom, in_bn=pro, dy_buf=bufs[dy_k])
+            tgt_k = self._take(bufs, (dy_k,))
+            self._claim(bufs[tgt_k])
+            da = self._view(bufs[tgt_k], b.src)
+            fuse = self.fuse_bn_bwd and op.full_cover
+            self._dgrad(op, dy, da, accumulate=False, bn=b if fuse else None, bn_x=b.src)
+            self._bn_bwd(b, b.src, da, da, reduced=fuse)
+            self._report(self.P.by_name[f"{b.bn.name}/gamma"].offset)
+            dy, dy_k = da, tgt_k
+        self._wgrad(self.images, dy, op0.dw, op0.geom, dy_buf=bufs[dy_k])
 
     def set_mix(self, table):
         """The mix table of the batch now in ex.images / ex.labels: numpy MIX_REC [N] or an int32
@@ -999,6 +1079,12 @@ class Executor:
             if self.check_nan:
                 self._check(self._view(bufs[cur], bp.x), f"input gradient of block {bp.blk.stage}.{bp.blk.index}")
             self._report(bp.grad_lo)
+        if self.deep:
+            self._tail_ev = None
+            self._deep_stem_bwd(bufs, cur)
+            self._report(0)
+            self._join()
+            return
         d_x0 = self._view(bufs[cur], self.blocks[0].x)
         st = self.stem_op
         pool_bwd = None

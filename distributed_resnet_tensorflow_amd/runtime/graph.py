@@ -10,6 +10,7 @@ collectives are host-issued RCCL calls use a chain of per-segment graphs instead
 """
 from __future__ import annotations
 
+import gc
 from typing import Callable
 
 import torch
@@ -26,8 +27,18 @@ class StepGraph:
                 step_fn()
         torch.cuda.current_stream().wait_stream(s)
         torch.cuda.synchronize()
-        with torch.cuda.graph(self.graph, pool=pool):
-            step_fn()
+        # No cyclic garbage collection inside the capture: a finalizer that destroys HIP objects there (the
+        # events of a dropped step plan, a P2P buffer) invalidates the capture and aborts the process. The
+        # step allocates ctypes argument blocks, so the collector would otherwise run at a point of its choice.
+        # (Only deferred, not forced: what is garbage now is freed when the collector next runs on its own.)
+        gc_was_on = gc.isenabled()
+        gc.disable()
+        try:
+            with torch.cuda.graph(self.graph, pool=pool):
+                step_fn()
+        finally:
+            if gc_was_on:
+                gc.enable()
         torch.cuda.synchronize()
 
     def replay(self):

@@ -74,6 +74,16 @@ def checkpoint_avg_down(FLAGS, prefix: str) -> bool:
     return was
 
 
+def checkpoint_deep_stem(FLAGS, prefix: str) -> bool:
+    """Whether the checkpoint was trained with the deep stem (its .meta; absent = False), so that evaluation
+    builds the network that was trained. An explicit --deep_stem that contradicts it is an error."""
+    was = Saver.restore_meta(prefix)["deep_stem"]
+    if "deep_stem" in FLAGS and FLAGS.is_present("deep_stem") and bool(FLAGS.deep_stem) != was:
+        raise FlagsError(f"--deep_stem={FLAGS.deep_stem} contradicts checkpoint {prefix}, whose .meta records "
+                         f"deep_stem={was} (drop the flag; the evaluator reads it from the .meta)")
+    return was
+
+
 def evaluate(FLAGS, eval_batch_size: int = 100, max_evals: int = -1):
     setup_logging(0)
     apply_thread_flags(FLAGS)
@@ -87,6 +97,8 @@ def evaluate(FLAGS, eval_batch_size: int = 100, max_evals: int = -1):
         FLAGS.se_ratio = checkpoint_se_ratio(FLAGS, first)
     if first is not None and "avg_down" in FLAGS:
         FLAGS.avg_down = checkpoint_avg_down(FLAGS, first)
+    if first is not None and "deep_stem" in FLAGS:
+        FLAGS.deep_stem = checkpoint_deep_stem(FLAGS, first)
     if "drop_path_rate" in FLAGS:
         FLAGS.drop_path_rate = 0.0   # stochastic depth shapes training steps only: the evaluated network is unscaled
     spec = model_spec_from_flags(FLAGS)

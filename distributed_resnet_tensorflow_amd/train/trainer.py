@@ -48,7 +48,8 @@ def model_spec_from_flags(FLAGS):
     return build_spec(ds, FLAGS.resnet_size, model=model, width=width, cardinality=FLAGS.cardinality,
                       width_per_group=FLAGS.width_per_group, se_ratio=getattr(FLAGS, "se_ratio", 0),
                       avg_down=bool(getattr(FLAGS, "avg_down", False)),
-                      drop_path_rate=float(getattr(FLAGS, "drop_path_rate", 0.0)))
+                      drop_path_rate=float(getattr(FLAGS, "drop_path_rate", 0.0)),
+                      deep_stem=bool(getattr(FLAGS, "deep_stem", False)))
 
 
 def _meta(FLAGS, spec):
@@ -63,6 +64,8 @@ def _meta(FLAGS, spec):
             **({"se_ratio": FLAGS.se_ratio} if getattr(FLAGS, "se_ratio", 0) else {}),
             # ResNet-D shortcuts only (absent = False)
             **({"avg_down": True} if getattr(FLAGS, "avg_down", False) else {}),
+            # deep stem only (absent = False)
+            **({"deep_stem": True} if getattr(FLAGS, "deep_stem", False) else {}),
             # stochastic depth only (absent = 0)
             **({"drop_path_rate": FLAGS.drop_path_rate} if getattr(FLAGS, "drop_path_rate", 0.0) else {}),
             "optimizer": FLAGS.optimizer, "eta": FLAGS.lars_eta, "eps": FLAGS.lars_eps,
